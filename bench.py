@@ -96,7 +96,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the get_loss-shaped step and the other secondary timings")
     ap.add_argument("--with-rollout", action="store_true", help="--config 5: run gsdyn.predict.predict_episode (GNN rollout + sharded renders, "
                     "one call per rank) over --steps frames and report rollout ms and render ms separately")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger outputs are cut to a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.config == 5 and args.with_rollout and args.steps < 2:
+        ap.error("--config 5 --with-rollout: --steps must be at least 2 (the rollout needs two frames)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -176,8 +183,9 @@ def main():
         dt = (time.perf_counter() - t0) / steps
         return dt, statistics.median(a.elapsed_time(b) for a, b in evs) * 1e-3, t_local
 
-    def measure(total_views, view_ids, with_opt, frozen_colours, want_roofline=True):
-        """One configuration: the step over `view_ids` of a `total_views`-camera ring (this rank's share), timed per the contract."""
+    def measure(total_views, view_ids, with_opt, frozen_colours, want_roofline=True, dump_dir=None):
+        """One configuration: the step over `view_ids` of a `total_views`-camera ring (this rank's share), timed per the contract.
+        ``dump_dir``: write the outputs of the last timed step there (``dump_outputs``)."""
         cams_all = synth_ring_cameras(total_views, W, H, device=dev)
         dL_all = torch.tensor(np.random.default_rng(1234).uniform(-1, 1, (total_views, 3, H, W)).astype(np.float32), device=dev)
         params = synth_scene_params(P_GAUSS, seed=0, device=dev)
@@ -190,6 +198,7 @@ def main():
         with_reduce = world > 1 or force_dist
         grad_out = bucket.views() if with_reduce else None     # the backward writes straight into the all-reduce bucket (no packing copy)
         ar_ev = [None]           # (start, end) HIP events around the all-reduce of ONE step, set by the separate pass below
+        last = {}                # the per-view outputs of the latest step (references only: nothing is copied in the timed region)
 
         def step():
             bucket.zero()
@@ -199,9 +208,11 @@ def main():
                     im, _, _ = rasterize_gaussians_views(cams, rv["means3D"], m2, rv["opacities"], colors_precomp=rv["colors_precomp"],
                                                          scales=rv["scales"], rotations=rv["rotations"])
                     im.backward(gradient=dL)
+                    last["images"] = im
                     m2.grad = None
                 else:
-                    _, g = render_step_views(params, cams, dL, want_colour_grad=not frozen_colours, grad_out=grad_out)
+                    ims, g = render_step_views(params, cams, dL, want_colour_grad=not frozen_colours, grad_out=grad_out)
+                    last.update(images=ims, means2D=g["means2D"], radii=g["radii"])
                     for k in GRAD_KEYS:
                         params[k].grad = g.get(k)
             if with_reduce:
@@ -237,6 +248,12 @@ def main():
         _hip.rasterize_forward_batch = orig_b
         torch.cuda.synchronize()
         t_step, t_event, t_local = timed(step, args.steps, args.warmup)
+        if dump_dir is not None and rank == 0:     # before any further step overwrites the buffers of the last timed one
+            outs = dict(last)
+            outs.update({f"grad_{k}": params[k].grad for k in GRAD_KEYS if params[k].grad is not None})
+            if with_opt:
+                outs.update({f"param_{k}": params[k] for k in GRAD_KEYS})
+            dump_outputs(dump_dir, outs)
         t_min = t_max = t_local
         if world > 1:
             t = torch.tensor([t_step, t_event, t_local, -t_local], device=dev, dtype=torch.float64)
@@ -290,7 +307,7 @@ def main():
     if default_n1:
         # ONE GPU, no flags: the top-level line is the configuration BASELINE.json's metric is quoted on (configs[2]: 4 x 800^2, fwd + bwd,
         # all gradients, no optimiser); the 8-view + Adam step of configs[3] -- what `--gpus N` times on N > 1 -- rides along as `scale_n1`
-        main_res = measure(4, list(range(4)), False, args.frozen_colours)
+        main_res = measure(4, list(range(4)), False, args.frozen_colours, dump_dir=args.dump_outputs)
         scale_n1 = measure(8, list(range(8)), True, args.frozen_colours)
         scale_n1["workload"] = ("configs[3] on ONE GPU: the fixed 8-view step (8x800^2, 100k Gaussians) fwd+bwd + Adam, all 8 views on this rank -- "
                                 "the N = 1 point of the strong-scaling curve `bench.py --gpus N` measures (N > 1: views r, r+N, ... per rank + 1 RCCL all-reduce)")
@@ -303,7 +320,7 @@ def main():
         total_views, my_ids, with_opt = 4, list(range(4)), False
     else:
         with_opt = not args.no_optimizer
-        main_res = measure(total_views, my_ids, with_opt, args.frozen_colours)
+        main_res = measure(total_views, my_ids, with_opt, args.frozen_colours, dump_dir=args.dump_outputs)
     if rank == 0 and world == 1 and not args.weak and args.config == 4 and not args.no_extras and not args.frozen_colours and not args.autograd:
         # the 8-view step with rgb_colors frozen, as the reference trains (no dL/dcolour: six sums per list entry)
         frozen = measure(8, list(range(8)), True, True, want_roofline=False)
@@ -349,6 +366,35 @@ def main():
     if world > 1 or force_dist:
         dist.destroy_process_group()
         _flush_c_stdio()
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays`` (name -> tensor) as ``out_dir/<name>.npy``: float64 stays float64, everything else becomes float32.  At most
+    DUMP_BUDGET_BYTES in all: taken smallest first, an array larger than an even share of what is left is cut to a sample of its
+    flattened elements at indices drawn from a generator seeded by its name and size -- the same elements in every run."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for k, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left, sampled = DUMP_BUDGET_BYTES - 256 * len(host), []      # (room for the .npy headers)
+    for i, k in enumerate(sorted(host, key=lambda k: (host[k].nbytes, k))):
+        a = host[k]
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(zlib.crc32(f"{k}:{a.size}".encode())).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(k)
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+        left -= a.nbytes
+    print(f"[bench] wrote {len(host)} outputs to {out_dir}" + (f" (sampled: {', '.join(sampled)})" if sampled else ""), file=sys.stderr)
 
 
 def _flush_c_stdio():
@@ -528,9 +574,11 @@ def bench_config5(args, dev, rank, world):
     shard = FrameShard(dev, W5, H5, ring_poses(CAMS, W5, H5), rank, world, speculative=False)
     pairs = shard.my_pairs(frames)
 
+    last = [{}]
+
     def run(n_frames, d=None):
         for f in range(n_frames):
-            shard.render_frame(f, data if d is None else d)
+            last[0] = shard.render_frame(f, data if d is None else d)
 
     num_rendered = []
     orig_b = _hip.rasterize_forward_batch
@@ -554,6 +602,8 @@ def bench_config5(args, dev, rank, world):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs is not None and rank == 0:     # this rank's cameras of the last timed frame
+        dump_outputs(args.dump_outputs, {f"cam{c}_{n}": t for c, ts in last[0].items() for n, t in zip(("image", "depth", "mask"), ts)})
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -683,6 +733,9 @@ def bench_config5_episode(args, dev, rank, world, params, P5, W5, H5, CAMS):
     if world > 1:
         dist.all_reduce(to, op=dist.ReduceOp.MAX)
     dt_overlap = float(to)
+    if args.dump_outputs is not None and rank == 0:     # the last frame of the timed episode, this rank's cameras
+        dump_outputs(args.dump_outputs, {f"cam{c}_{n}": t for (f, c), ts in out.items() if f == frames - 1
+                                         for n, t in zip(("image", "depth", "mask"), ts)})
     # the pipelined episode (predict_episode(pipeline=True)): rank 0 rolls out and broadcasts one 8.8 KB skinning packet per moving step, the
     # other ranks move the Gaussians with it (one skinning launch per frame) and render.  world = 1: its two sides are timed separately
     # on this GPU -- the producer's streaming rollout with a packet hook, and a render rank's frame production from recorded packets --

@@ -306,6 +306,7 @@ def test_row_wise_error_against_the_fp64_oracle(dev, P, W, H, seed):
     color, radii, depth, grads, _ = _run_hip(cam, g, dev, dL=dL)
     assert np.array_equal(radii, o32.radii)
     assert np.abs(color[:, ok] - o64.color[:, ok]).max() < 2e-5
+    os.makedirs(os.path.dirname(_ROW_LOG), exist_ok=True)
     with open(_ROW_LOG, "a") as f:
         for k in ("means3D", "means2D", "colors_precomp", "opacities", "scales", "rotations"):
             e_hip, r_hip = row_err(grads[k], g64[k])
