@@ -34,7 +34,8 @@ def build(verbose=False):
            "-Wno-deprecated-declarations"]
     cmd += [f"-I{p}" for p in inc]
     cmd += [SRC, "-o", OUT, f"-L{libdir}", "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python",
-            f"-L{HERE}", "-lgsr_hip", "-Wl,-rpath,$ORIGIN/../csrc", f"-Wl,-rpath,{libdir}"]
+            f"-L{HERE}", "-lgsr_hip", "-Wl,-rpath,$ORIGIN/../csrc", f"-Wl,-rpath,{libdir}",
+            "-Wl,-z,now"]   # every libgsr_hip.so symbol resolved at import: a stale library without an entry point this layer calls fails loudly there
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -92,6 +92,8 @@ size_t gsr_geom_bytes(int32_t P) { GeomState g; return gsr_carve_geom(nullptr, P
 size_t gsr_image_bytes(int32_t H, int32_t W) { ImageState im; return gsr_carve_image(nullptr, H, W, &im); }
 size_t gsr_binning_bytes(uint32_t D, int32_t, int32_t) { BinningState b; return gsr_carve_binning(nullptr, D, &b); }
 size_t gsr_backward_scratch_bytes(int32_t, uint32_t D) { return gsr_align((size_t)(D ? D : 1) * GSR_PARTIAL_FLOATS * 4); }
+// the records, then one float of dL/dz per entry (gsr_depth_scratch_offset)
+size_t gsr_backward_scratch_bytes_depth(int32_t, uint32_t D) { return gsr_depth_scratch_offset(D) + gsr_align((size_t)(D ? D : 1) * 4); }
 
 // ---------------------------------------------------------------------------------------- table builders
 }  // extern "C"
@@ -495,13 +497,15 @@ int gsr_forward_render_shared_ex(const gsr_settings* s, int32_t P, uint32_t num_
   return gsr_launch_render_fwd(rt, st);
 }
 
-int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                 const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                 const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                 const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream) {
-  GsrRange _range("gsr_backward");
+}  // extern "C"
+// gsr_backward and gsr_backward_depth: dL_ddepth == nullptr is exactly gsr_backward
+static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                        const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                        const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                        const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream) {
+  GsrRange _range(dL_ddepth ? "gsr_backward_depth" : "gsr_backward");
   GsrCam cam;
   if (int rc = make_cam(s, &cam)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -516,17 +520,52 @@ int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const 
   gsr_carve_image(const_cast<void*>(image_state), cam.H, cam.W, &im);
   gsr_carve_binning(const_cast<void*>(binning_state), num_rendered, &bs);
   float4* partials = (float4*)scratch;
+  // depth: the per-entry dL/dz behind the records (scratch of gsr_backward_scratch_bytes_depth bytes); no entries, no depth term
+  float* dL_dz = (dL_ddepth && num_rendered > 0) ? (float*)((char*)scratch + gsr_depth_scratch_offset(num_rendered)) : nullptr;
   if (num_rendered > 0) {
     GsrRenderViews rt;
     render_header(rt, 1, cam, im.tile_order, im.queue);
     rt.no_colour_grad = (!shs && !dL_dcolors) ? 1 : 0;   // precomputed colours and no gradient wanted for them
     rt.avg_list = num_rendered / (uint32_t)(cam.T > 0 ? cam.T : 1);
     fill_render_view(rt.v[0], cam, g, bs, im, nullptr, nullptr, dL_dcolor, partials);
-    if (int rc = gsr_launch_render_bwd(rt, st)) return rc;
+    GsrDepthViews dv;
+    if (dL_dz) { dv.dL_ddepth[0] = dL_ddepth; dv.dL_dz[0] = dL_dz; }
+    if (int rc = gsr_launch_render_bwd(rt, st, dL_dz ? &dv : nullptr)) return rc;
   }
   return gsr_launch_preprocess_bwd(cam, P, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, g,
                                    partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales,
-                                   dL_drotations, dL_dcov3D, dL_dsh, num_rendered > 0 ? im.queue + GSR_QUEUE_BWD_ERROR : nullptr, st);
+                                   dL_drotations, dL_dcov3D, dL_dsh, num_rendered > 0 ? im.queue + GSR_QUEUE_BWD_ERROR : nullptr, st, dL_dz);
+}
+extern "C" {
+int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                 const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                 const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                 const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream) {
+  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
+                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                      dL_dcov3D, dL_dsh, nullptr, stream);
+}
+}  // extern "C"
+static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                          const float* scales, const float* rotations, const float* colors_precomp,
+                          const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                          void* const* binning_states, void* const* image_states, void* batch_state,
+                          const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                          float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                          float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw,
+                          const float* const* dL_ddepth_views, void* stream);
+extern "C" {
+int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                       const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                       const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                       const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                       float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream) {
+  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
+                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                      dL_dcov3D, dL_dsh, dL_ddepth, stream);
 }
 
 // ------------------------------------------------------------------------------------------ multi-view batch
@@ -674,6 +713,19 @@ int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32
                                 dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, stream);
 }
 
+int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                             const float* scales, const float* rotations, const float* colors_precomp,
+                             const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                             void* const* binning_states, void* const* image_states, void* batch_state,
+                             const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                             float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                             void* stream) {
+  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, stream);
+}
+
 int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp,
                        const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
@@ -682,7 +734,23 @@ int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const ui
                        float* const* dL_dmeans2D,
                        float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
                        float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, void* stream) {
-  GsrRange _range("gsr_backward_batch");
+  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, raw, nullptr, stream);
+}
+}  // extern "C"
+
+// gsr_backward_batch_raw and gsr_backward_batch_depth: dL_ddepth_views == nullptr (or all of its entries nullptr) is exactly the former
+static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                       const float* scales, const float* rotations, const float* colors_precomp,
+                       const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                       void* const* binning_states, void* const* image_states, void* batch_state,
+                       const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                       float* const* dL_dmeans2D,
+                       float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
+                       float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, const float* const* dL_ddepth_views,
+                       void* stream) {
+  GsrRange _range(dL_ddepth_views ? "gsr_backward_batch_depth" : "gsr_backward_batch");
   if (int rc = check_batch("gsr_backward_batch", V, s, batch_state)) return rc;
   if (int rc = check_geometry_of(V, geometry_of)) return rc;
   if (!num_rendered || !radii || !geom_states || !binning_states || !image_states || !dL_dcolor || !scratch ||
@@ -718,7 +786,10 @@ int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const ui
   pair_up(V, geometry_of, num_rendered, partner, fused);
   bool pairs_fwd = false;
   for (int v = 0; v < V; ++v) pairs_fwd = pairs_fwd || fused[v];
-  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views;
+  bool depth = false;   // a depth gradient for some view: the depth build, which has no fused pairs (the call runs unfused)
+  for (int v = 0; dL_ddepth_views && v < V; ++v) depth = depth || dL_ddepth_views[v] != nullptr;
+  GsrDepthViews dv;
+  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth;
   if (!fuse_bwd)
     for (int v = 0; v < V; ++v) { partner[v] = -1; fused[v] = 0; }
   for (int v = 0; v < V; ++v) {
@@ -747,13 +818,19 @@ int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const ui
     w.fused_alias = fused[v];
     w.cap = num_rendered[v];
     w.W = cam.W; w.H = cam.H; w.tanfovx = cam.tanfovx; w.tanfovy = cam.tanfovy;
+    if (depth) {   // every view's scratch holds gsr_backward_scratch_bytes_depth(P, num_rendered[v]): the blend writes dL/dz for all of them
+      dv.dL_ddepth[v] = dL_ddepth_views[v];
+      dv.dL_dz[v] = num_rendered[v] > 0 ? (float*)((char*)scratch[v] + gsr_depth_scratch_offset(num_rendered[v])) : nullptr;
+    }
   }
+  GsrDepthViews dvp = dv;   // the per-Gaussian backward: only views with a depth gradient add the depth term
+  for (int v = 0; depth && v < V; ++v) if (!dv.dL_ddepth[v]) dvp.dL_dz[v] = nullptr;
   if (any) {
     { uint64_t tot = 0; for (int v = 0; v < V; ++v) tot += num_rendered[v]; rt.avg_list = (uint32_t)(tot / ((uint64_t)V * (uint64_t)(rt.T > 0 ? rt.T : 1))); }
     const bool rebuild = pairs_fwd && !fuse_bwd;
     if (rebuild)
       if (int rc = gsr_launch_tile_order(bt, st)) return rc;
-    if (int rc = gsr_launch_render_bwd(rt, st)) return rc;
+    if (int rc = gsr_launch_render_bwd(rt, st, depth ? &dv : nullptr)) return rc;
     vw.bwd_error = rt.queue + GSR_QUEUE_BWD_ERROR;
     if (rebuild) {
       pair_up(V, geometry_of, num_rendered, partner, fused);
@@ -763,8 +840,9 @@ int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const ui
   }
   (void)colors_precomp;
   return gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
-                                         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st);
+                                         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st, (depth && any) ? &dvp : nullptr);
 }
+extern "C" {
 
 int32_t gsr_rigidity_blocks(int32_t n_fg) { return gsr_rigidity_fwd_blocks(n_fg); }
 

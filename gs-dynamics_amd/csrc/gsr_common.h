@@ -293,13 +293,19 @@ int gsr_launch_shared_lists(const GsrBinViews& tab, int P, uint32_t D, const uin
                             const uint32_t* owner_queue, uint2* ranges, uint4* order, uint32_t* queue, hipStream_t st);
 int gsr_launch_gather_counts(const GsrBinViews& tab, int P, uint32_t* counts_dev, hipStream_t st);   // counts_dev[v] = offsets_v[P]   // uses only V, T, order, queue, v[].ranges, v[].fused_alias
 int gsr_launch_render_fwd(const GsrRenderViews& tab, hipStream_t st);
-int gsr_launch_render_bwd(const GsrRenderViews& tab, hipStream_t st);
+// Differentiable depth (gsr_backward_depth / gsr_backward_batch_depth): per view, the incoming dL/ddepth image [H,W] (nullptr: none for
+// this view) and the per-entry dL/dz array [num_rendered] the blend backward writes (indexed like the records; read by the per-Gaussian
+// backward, which adds dL/dz * (view[2], view[6], view[10]) to dL/dmeans3D).
+struct GsrDepthViews { const float* dL_ddepth[GSR_MAX_BATCH]; float* dL_dz[GSR_MAX_BATCH]; };
+// the scratch of a depth backward: the record array (gsr_backward_scratch_bytes), then the dL/dz array
+static inline size_t gsr_depth_scratch_offset(uint32_t D) { return gsr_align((size_t)(D ? D : 1) * GSR_PARTIAL_FLOATS * 4); }
+int gsr_launch_render_bwd(const GsrRenderViews& tab, hipStream_t st, const GsrDepthViews* depth = nullptr);
 int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, const float* scales,
                               const float* rotations, const float* colors_precomp, const float* shs,
                               const float* cov3D_precomp, const int32_t* radii, const GeomState& g,
                               const float4* partials, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                               float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                              float* dL_dsh, const uint32_t* bwd_error, hipStream_t st);
+                              float* dL_dsh, const uint32_t* bwd_error, hipStream_t st, const float* dL_dz = nullptr);
 // Per-view pointers of the multi-view preprocess backward (passed by value as a kernel argument).
 struct GsrBwdView {
   const float *view, *proj;
@@ -329,7 +335,7 @@ struct GsrBwdViews {
 int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_modifier, const float* means3D,
                                     const float* scales, const float* rotations, const float* cov3D_precomp,
                                     float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
-                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st);
+                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth = nullptr);
 int gsr_launch_image_loss_fwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, float* fA,
                               float* fC, float* fE, float* block_l1, float* block_ssim, hipStream_t st);
 int gsr_launch_image_loss_bwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, const float* fA,

@@ -127,6 +127,13 @@ __device__ __forceinline__ PartialSum reduce_partials(const float4* __restrict__
   ps.dr = col ? r1.z : 0.f; ps.dg = col ? r1.w : 0.f; ps.db = col ? r2x : 0.f;
   return ps;
 }
+// The depth path of the reduce: dL/dz of a Gaussian = the sum of its entries' dL/dz (the blend backward's depth build writes one float per
+// entry, indexed like the records), in the same ascending order.
+__device__ __forceinline__ float reduce_partials_dz(const float* __restrict__ dL_dz, uint32_t e0, uint32_t e1) {
+  float gz = 0.f;
+  for (uint32_t e = e0; e < e1; ++e) gz += dL_dz[e];
+  return gz;
+}
 
 // The per-Gaussian chain (3D covariance, conic -> cov2D -> cov3D / view-space mean, cov3D -> scale / rotation) runs in DOUBLE precision
 // (round 6).  It is a chain of differences of nearly equal products -- det = a c - b b, the inverse of the 2D covariance, the congruence
@@ -171,10 +178,13 @@ __device__ __forceinline__ void build_cov3(int i, float mod, const float* __rest
 
 // One view's chain: conic -> cov2D -> (cov3D, view-space mean) and 2D mean -> 3D mean.  ACCUMULATES into
 // gcov[6] and gm3[3]; returns this view's dL/d(NDC mean) in gm2.
+// DEPTH: gz = dL/d(view-space depth) of the Gaussian from the depth image; depth IS tz (no frustum clamp on it), so it joins dL/dtz and
+// reaches dL/dmeans3D as gz * (view[2], view[6], view[10]) inside the fp64 sum.
+template <bool DEPTH = false>
 __device__ __forceinline__ void view_chain(const float* __restrict__ view, const float* __restrict__ proj, int W, int H,
                                            float tanfovx, float tanfovy, float3 p, const real c[6],
                                            const PartialSum& ps, float gcov[6], float gm3[3], float gm2[2],
-                                           float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr) {
+                                           float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr, float gz = 0.f) {
   const real pvx = (real)view[0] * p.x + view[4] * p.y + view[8] * p.z + view[12];
   const real pvy = (real)view[1] * p.x + view[5] * p.y + view[9] * p.z + view[13];
   const real pvz = (real)view[2] * p.x + view[6] * p.y + view[10] * p.z + view[14];
@@ -223,7 +233,8 @@ __device__ __forceinline__ void view_chain(const float* __restrict__ view, const
   const real itz = 1.0f / tz, itz2 = itz * itz, itz3 = itz2 * itz;
   const real dtx = xm * -fx * itz2 * dJ02;
   const real dty = ym * -fy * itz2 * dJ12;
-  const real dtz = -fx * itz2 * dJ00 - fy * itz2 * dJ11 + (2.0f * fx * tx) * itz3 * dJ02 + (2.0f * fy * ty) * itz3 * dJ12;
+  real dtz = -fx * itz2 * dJ00 - fy * itz2 * dJ11 + (2.0f * fx * tx) * itz3 * dJ02 + (2.0f * fy * ty) * itz3 * dJ12;
+  if (DEPTH) dtz += (real)gz;
   // the blend backward hands over the raw sums of t*dx and t*dy (ps.gmx, ps.gmy); with the conic
   // (A, B, C) = (cc, -b, a) / det:  d/d mean2D.x = -(A sx + B sy),  d/d mean2D.y = -(C sy + B sx)
   const real det_inv = 1.0f / det;
@@ -274,222 +285,14 @@ __device__ __forceinline__ bool gsr_view_used(const GsrBwdView& w, int i) {
   return !w.used || !w.tracked || *w.tracked == 0u || w.used[i] != 0;
 }
 
-// ---- single view ------------------------------------------------------------------------------------
-template <bool USE_SH>
-__global__ __launch_bounds__(GSR_BLOCK) void preprocess_bwd_kernel(
-    int P, int W, int H, float tanfovx, float tanfovy, float mod, int sh_degree, int M,
-    const float* __restrict__ view, const float* __restrict__ proj, const float* __restrict__ campos,
-    const float* __restrict__ means3D, const float* __restrict__ scales, const float* __restrict__ rotations,
-    const float* __restrict__ colors_precomp, const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
-    const int32_t* __restrict__ radii, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ clamped,
-    const float4* __restrict__ partials, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D,
-    float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
-    const uint8_t* __restrict__ used, const uint32_t* __restrict__ tracked, const uint32_t* __restrict__ bwd_error) {
-  const int i = blockIdx.x * GSR_BLOCK + threadIdx.x;
-  if (i >= P) return;
-  float gm3[3] = {0.f, 0.f, 0.f}, gm2[2] = {0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f;
-  float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const bool alive = radii[i] > 0 && (!used || !tracked || *tracked == 0u || used[i] != 0);   // (see gsr_view_used)
-  if (USE_SH && !alive && dL_dsh) {
-    for (int k = 0; k < M * 3; ++k) dL_dsh[(size_t)i * M * 3 + k] = 0.f;
-  }
-  if (alive) {
-    const PartialSum ps = reduce_partials(partials, offsets[i], offsets[i + 1], USE_SH || dL_dcolors != nullptr);
-    gop = ps.gop;
-    const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-    if (USE_SH) {
-      float dmean_sh[3] = {0.f, 0.f, 0.f};
-      sh_backward(sh_degree, M, shs + (size_t)i * M * 3, p, campos, clamped[i], ps.dr, ps.dg, ps.db,
-                  dL_dsh + (size_t)i * M * 3, dmean_sh);
-      gm3[0] = dmean_sh[0]; gm3[1] = dmean_sh[1]; gm3[2] = dmean_sh[2];
-    } else {
-      gcol[0] = ps.dr; gcol[1] = ps.dg; gcol[2] = ps.db;
-    }
-    Cov3 cv;
-    build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
-    view_chain(view, proj, W, H, tanfovx, tanfovy, p, cv.c, ps, gcov, gm3, gm2);
-    if (!cov3D_precomp) cov3_to_scale_rot(cv, mod, gcov, gs, gq);
-  }
-  if (bwd_error && *bwd_error != 0u) gm3[0] = gm3[1] = gm3[2] = __builtin_nanf("");   // the blend backward of this call aborted: loud, not garbage (GSR_QUEUE_BWD_ERROR)
-  dL_dmeans3D[3 * i] = gm3[0]; dL_dmeans3D[3 * i + 1] = gm3[1]; dL_dmeans3D[3 * i + 2] = gm3[2];
-  dL_dmeans2D[3 * i] = gm2[0]; dL_dmeans2D[3 * i + 1] = gm2[1]; dL_dmeans2D[3 * i + 2] = 0.f;
-  if (dL_dcolors) { dL_dcolors[3 * i] = gcol[0]; dL_dcolors[3 * i + 1] = gcol[1]; dL_dcolors[3 * i + 2] = gcol[2]; }
-  dL_dopacity[i] = gop;
-  if (dL_dscales) { dL_dscales[3 * i] = gs[0]; dL_dscales[3 * i + 1] = gs[1]; dL_dscales[3 * i + 2] = gs[2]; }
-  if (dL_drot) { dL_drot[4 * i] = gq[0]; dL_drot[4 * i + 1] = gq[1]; dL_drot[4 * i + 2] = gq[2]; dL_drot[4 * i + 3] = gq[3]; }
-  if (dL_dcov3D) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = gcov[k];
-  }
-}
-
-// ---- all views of a step at once (precomputed colours) ----------------------------------------------
-// One lane per Gaussian loops over the V views: per view it reduces that view's entry records and runs the
-// view-dependent chain; colour / opacity / mean / cov3D gradients are summed in registers and the
-// scale/rotation chain (linear in dL/dcov3D) runs once.  Replaces V kernels + the host-side sums over views.
-__global__ __launch_bounds__(GSR_BLOCK) void preprocess_bwd_views_kernel(
-    GsrBwdViews vw, int P, float mod, const float* __restrict__ means3D, const float* __restrict__ scales,
-    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, float* __restrict__ dL_dmeans3D,
-    float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D) {
-  const int i = blockIdx.x * GSR_BLOCK + threadIdx.x;
-  if (i >= P) return;
-  float gm3[3] = {0.f, 0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f;
-  float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f}, gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-  Cov3 cv;
-  build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
-  bool any = false;
-  for (int v = 0; v < vw.V; ++v) {
-    const GsrBwdView& w = vw.v[v];
-    if (w.fused_alias) continue;      // its owner's records carry it (fused pair): the owner writes its dL_dmeans2D too
-    float gm2[2] = {0.f, 0.f}, gm2a[2] = {0.f, 0.f};
-    const bool pair = w.partner_dL_dmeans2D != nullptr;
-    if (w.radii[i] > 0 && gsr_view_used(w, i)) {
-      any = true;
-      const PartialSum ps = reduce_partials(w.partials, min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap),
-                                            pair || w.dL_dcolors != nullptr || dL_dcolors != nullptr);
-      gop += ps.gop;
-      if (pair) {   // record layout of the pair backward: geometry sums of both views, then (sum t dx, sum t dy) of this view alone
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a);
-      } else {
-        if (w.dL_dcolors) { w.dL_dcolors[3 * i] = ps.dr; w.dL_dcolors[3 * i + 1] = ps.dg; w.dL_dcolors[3 * i + 2] = ps.db; }
-        else { gcol[0] += ps.dr; gcol[1] += ps.dg; gcol[2] += ps.db; }
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2);
-      }
-    } else if (w.dL_dcolors) {
-      w.dL_dcolors[3 * i] = 0.f; w.dL_dcolors[3 * i + 1] = 0.f; w.dL_dcolors[3 * i + 2] = 0.f;
-    }
-    if (pair) {
-      w.dL_dmeans2D[3 * i] = gm2a[0]; w.dL_dmeans2D[3 * i + 1] = gm2a[1]; w.dL_dmeans2D[3 * i + 2] = 0.f;
-      float* m2b = w.partner_dL_dmeans2D;
-      m2b[3 * i] = gm2[0] - gm2a[0]; m2b[3 * i + 1] = gm2[1] - gm2a[1]; m2b[3 * i + 2] = 0.f;
-    } else {
-      w.dL_dmeans2D[3 * i] = gm2[0]; w.dL_dmeans2D[3 * i + 1] = gm2[1]; w.dL_dmeans2D[3 * i + 2] = 0.f;
-    }
-  }
-  if (any && !cov3D_precomp) cov3_to_scale_rot(cv, mod, gcov, gs, gq);
-  if (vw.bwd_error && *vw.bwd_error != 0u) gm3[0] = gm3[1] = gm3[2] = __builtin_nanf("");   // the blend backward of this call aborted: loud, not garbage (GSR_QUEUE_BWD_ERROR)
-  dL_dmeans3D[3 * i] = gm3[0]; dL_dmeans3D[3 * i + 1] = gm3[1]; dL_dmeans3D[3 * i + 2] = gm3[2];
-  if (dL_dcolors) { dL_dcolors[3 * i] = gcol[0]; dL_dcolors[3 * i + 1] = gcol[1]; dL_dcolors[3 * i + 2] = gcol[2]; }
-  if (vw.d_raw_rot) {   // raw-parameter mode: the chain through normalize / sigmoid / exp, here instead of in a launch of its own
-    reinterpret_cast<float4*>(vw.d_raw_rot)[i] =
-        gsr_act_rotation_bwd(reinterpret_cast<const float4*>(vw.raw_rot)[i], make_float4(gq[0], gq[1], gq[2], gq[3]));
-    const float o = vw.act_op[i];
-    vw.d_raw_op[i] = gop * o * (1.0f - o);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vw.d_raw_sc[3 * (size_t)i + k] = gs[k] * vw.act_sc[3 * (size_t)i + k];
-  }
-  if (dL_dopacity) dL_dopacity[i] = gop;
-  if (dL_dscales) { dL_dscales[3 * i] = gs[0]; dL_dscales[3 * i + 1] = gs[1]; dL_dscales[3 * i + 2] = gs[2]; }
-  if (dL_drot) { dL_drot[4 * i] = gq[0]; dL_drot[4 * i + 1] = gq[1]; dL_drot[4 * i + 2] = gq[2]; dL_drot[4 * i + 3] = gq[3]; }
-  if (dL_dcov3D) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = gcov[k];
-  }
-}
-
-// ---- all views of a step at once, ONE WAVE PER VIEW (V >= 2) ------------------------------------------
-// The loop above walks the views strictly load -> chain -> load at 1.5 waves per SIMD: 62 us for 8 views of 100 k Gaussians, 22 % of the
-// HBM roofline.  Here a workgroup owns 64 Gaussians and has one wave per (non-alias) view: the view is wave-uniform (its matrices and
-// pointers stay scalar loads), every wave reduces its view's records and runs that view's chain for the 64 Gaussians, parks its 13
-// per-Gaussian sums in LDS ([view][value][lane]: conflict-free), and wave 0 adds the views up in view order -- the same order of
-// additions as the loop, hence the same bits -- and finishes with the view-independent part (scale / rotation chain, activations).
-// V x more waves in flight, no second pass over HBM.
-#define PBW_VALUES 13      // gcov[6], gm3[3], gop, gcol[3]
-// (No occupancy bound: with the chain in fp64 the kernel needs 166 VGPRs; bounded to the fp32 build's 80 it spilled and took 70 us at four views.)
-template <int MAXW>      // waves per workgroup the instantiation is compiled for (= views it can take): its register budget follows
-__global__ __launch_bounds__(64 * MAXW) void preprocess_bwd_views_waves_kernel(
-    GsrBwdViews vw, int P, float mod, const float* __restrict__ means3D, const float* __restrict__ scales,
-    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, float* __restrict__ dL_dmeans3D,
-    float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D) {
-  extern __shared__ float s_part[];                  // [waves][PBW_VALUES + 1][64]  (+1: "this view saw the Gaussian")
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
-  const int i = blockIdx.x * 64 + lane;
-  const bool live = i < P;
-  // wave wv's view: the wv-th view that is not a fused alias (uniform: scalar code)
-  int v = -1;
-  for (int u = 0, k = 0; u < vw.V; ++u)
-    if (!vw.v[u].fused_alias) { if (k == wv) { v = u; break; } ++k; }
-  const GsrBwdView& w = vw.v[v < 0 ? 0 : v];
-  float3 p = make_float3(0.f, 0.f, 0.f);
-  Cov3 cv;
-  if (live) {
-    p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-    build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
-  }
-  float gm3[3] = {0.f, 0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f, gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float seen = 0.f;
-  if (live && v >= 0) {
-    float gm2[2] = {0.f, 0.f}, gm2a[2] = {0.f, 0.f};
-    const bool pair = w.partner_dL_dmeans2D != nullptr;
-    if (w.radii[i] > 0 && gsr_view_used(w, i)) {
-      seen = 1.f;
-      const PartialSum ps = reduce_partials(w.partials, min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap),
-                                            pair || w.dL_dcolors != nullptr || dL_dcolors != nullptr);
-      gop = ps.gop;
-      if (pair) {
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a);
-      } else {
-        if (w.dL_dcolors) { w.dL_dcolors[3 * i] = ps.dr; w.dL_dcolors[3 * i + 1] = ps.dg; w.dL_dcolors[3 * i + 2] = ps.db; }
-        else { gcol[0] = ps.dr; gcol[1] = ps.dg; gcol[2] = ps.db; }
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2);
-      }
-    } else if (w.dL_dcolors) {
-      w.dL_dcolors[3 * i] = 0.f; w.dL_dcolors[3 * i + 1] = 0.f; w.dL_dcolors[3 * i + 2] = 0.f;
-    }
-    if (pair) {
-      w.dL_dmeans2D[3 * i] = gm2a[0]; w.dL_dmeans2D[3 * i + 1] = gm2a[1]; w.dL_dmeans2D[3 * i + 2] = 0.f;
-      float* m2b = w.partner_dL_dmeans2D;
-      m2b[3 * i] = gm2[0] - gm2a[0]; m2b[3 * i + 1] = gm2[1] - gm2a[1]; m2b[3 * i + 2] = 0.f;
-    } else {
-      w.dL_dmeans2D[3 * i] = gm2[0]; w.dL_dmeans2D[3 * i + 1] = gm2[1]; w.dL_dmeans2D[3 * i + 2] = 0.f;
-    }
-  }
-  float* mine = s_part + (size_t)wv * (PBW_VALUES + 1) * 64 + lane;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) mine[k * 64] = gcov[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { mine[(6 + k) * 64] = gm3[k]; mine[(10 + k) * 64] = gcol[k]; }
-  mine[9 * 64] = gop;
-  mine[PBW_VALUES * 64] = seen;
-  __syncthreads();
-  if (wv != 0 || !live) return;
-  // view order: the loop kernel adds view 0's terms to zero-initialised sums first -- start from this wave's own values (view order
-  // = wave order) and add the others in order
-  bool any = seen != 0.f;
-  for (int u = 1; u < nw; ++u) {
-    const float* q = s_part + (size_t)u * (PBW_VALUES + 1) * 64 + lane;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) gcov[k] += q[k * 64];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { gm3[k] += q[(6 + k) * 64]; gcol[k] += q[(10 + k) * 64]; }
-    gop += q[9 * 64];
-    any = any || q[PBW_VALUES * 64] != 0.f;
-  }
-  float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
-  if (any && !cov3D_precomp) cov3_to_scale_rot(cv, mod, gcov, gs, gq);
-  if (vw.bwd_error && *vw.bwd_error != 0u) gm3[0] = gm3[1] = gm3[2] = __builtin_nanf("");   // the blend backward of this call aborted: loud, not garbage (GSR_QUEUE_BWD_ERROR)
-  dL_dmeans3D[3 * i] = gm3[0]; dL_dmeans3D[3 * i + 1] = gm3[1]; dL_dmeans3D[3 * i + 2] = gm3[2];
-  if (dL_dcolors) { dL_dcolors[3 * i] = gcol[0]; dL_dcolors[3 * i + 1] = gcol[1]; dL_dcolors[3 * i + 2] = gcol[2]; }
-  if (vw.d_raw_rot) {
-    reinterpret_cast<float4*>(vw.d_raw_rot)[i] =
-        gsr_act_rotation_bwd(reinterpret_cast<const float4*>(vw.raw_rot)[i], make_float4(gq[0], gq[1], gq[2], gq[3]));
-    const float o = vw.act_op[i];
-    vw.d_raw_op[i] = gop * o * (1.0f - o);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vw.d_raw_sc[3 * (size_t)i + k] = gs[k] * vw.act_sc[3 * (size_t)i + k];
-  }
-  if (dL_dopacity) dL_dopacity[i] = gop;
-  if (dL_dscales) { dL_dscales[3 * i] = gs[0]; dL_dscales[3 * i + 1] = gs[1]; dL_dscales[3 * i + 2] = gs[2]; }
-  if (dL_drot) { dL_drot[4 * i] = gq[0]; dL_drot[4 * i + 1] = gq[1]; dL_drot[4 * i + 2] = gq[2]; dL_drot[4 * i + 3] = gq[3]; }
-  if (dL_dcov3D) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = gcov[k];
-  }
-}
+// The three kernels are written once (gsr_preprocess_bwd_kernels.inc) and compiled twice: GSR_PBWD_DEPTH 0 gives the kernels of
+// gsr_backward / gsr_backward_batch, 1 their differentiable-depth builds (*_depth_kernel: one more argument, the per-entry dL/dz).
+#define GSR_PBWD_DEPTH 0
+#include "gsr_preprocess_bwd_kernels.inc"
+#undef GSR_PBWD_DEPTH
+#define GSR_PBWD_DEPTH 1
+#include "gsr_preprocess_bwd_kernels.inc"
+#undef GSR_PBWD_DEPTH
 
 }  // namespace gsr_preprocess_bwd
 using namespace gsr_preprocess_bwd;
@@ -499,15 +302,19 @@ int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, co
                               const float* cov3D_precomp, const int32_t* radii, const GeomState& g,
                               const float4* partials, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors,
                               float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                              float* dL_dsh, const uint32_t* bwd_error, hipStream_t st) {
+                              float* dL_dsh, const uint32_t* bwd_error, hipStream_t st, const float* dL_dz) {
   if (P <= 0) return 0;
   const dim3 grid((P + GSR_BLOCK - 1) / GSR_BLOCK), block(GSR_BLOCK);
 #define GSR_PBWD_ARGS                                                                                              \
   P, cam.W, cam.H, cam.tanfovx, cam.tanfovy, cam.scale_modifier, cam.sh_degree, cam.M, cam.view, cam.proj,       \
       cam.campos, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, g.offsets, g.clamped,  \
       partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dsh, g.used, g.counters + 1, bwd_error
-  if (shs) {
-    if (!dL_dsh) { gsr_set_error("gsr_backward: shs given but dL_dsh is NULL"); return -2; }
+  if (shs && !dL_dsh) { gsr_set_error("gsr_backward: shs given but dL_dsh is NULL"); return -2; }
+  if (dL_dz) {   // differentiable depth (gsr_backward_depth)
+    { GSR_PROF("preprocess_bwd_depth", st);
+      if (shs) hipLaunchKernelGGL(preprocess_bwd_depth_kernel<true>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz);
+      else hipLaunchKernelGGL(preprocess_bwd_depth_kernel<false>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz); }
+  } else if (shs) {
     { GSR_PROF("preprocess_bwd", st);
   hipLaunchKernelGGL(preprocess_bwd_kernel<true>, grid, block, 0, st, GSR_PBWD_ARGS); }
   } else {
@@ -522,7 +329,7 @@ int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, co
 int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_modifier, const float* means3D,
                                     const float* scales, const float* rotations, const float* cov3D_precomp,
                                     float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
-                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st) {
+                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth) {
   if (P <= 0) return 0;
   int nact = 0;
   for (int v = 0; v < vw.V; ++v) nact += vw.v[v].fused_alias ? 0 : 1;
@@ -531,13 +338,23 @@ int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_mo
 #define PBW_LAUNCH(MAXW) hipLaunchKernelGGL(preprocess_bwd_views_waves_kernel<MAXW>, dim3((P + 63) / 64), dim3(64 * nact),              \
                            sizeof(float) * (size_t)nact * (PBW_VALUES + 1) * 64, st, vw, P, scale_modifier, means3D, scales, rotations,       \
                            cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D)
-      if (nact <= 4) PBW_LAUNCH(4); else if (nact <= 8) PBW_LAUNCH(8); else PBW_LAUNCH(GSR_MAX_BATCH);
+#define PBW_LAUNCH_DEPTH(MAXW) hipLaunchKernelGGL(preprocess_bwd_views_waves_depth_kernel<MAXW>, dim3((P + 63) / 64), dim3(64 * nact),  \
+                           sizeof(float) * (size_t)nact * (PBW_VALUES + 1) * 64, st, vw, P, scale_modifier, means3D, scales, rotations,       \
+                           cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, *depth)
+      if (depth) { if (nact <= 4) PBW_LAUNCH_DEPTH(4); else if (nact <= 8) PBW_LAUNCH_DEPTH(8); else PBW_LAUNCH_DEPTH(GSR_MAX_BATCH); }
+      else if (nact <= 4) PBW_LAUNCH(4); else if (nact <= 8) PBW_LAUNCH(8); else PBW_LAUNCH(GSR_MAX_BATCH);
 #undef PBW_LAUNCH
+#undef PBW_LAUNCH_DEPTH
     }
     GSR_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  { GSR_PROF("preprocess_bwd_views", st);
+  if (depth) {
+    GSR_PROF("preprocess_bwd_views", st);
+    hipLaunchKernelGGL(preprocess_bwd_views_depth_kernel, dim3((P + GSR_BLOCK - 1) / GSR_BLOCK), dim3(GSR_BLOCK), 0, st, vw, P,
+                       scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity,
+                       dL_dscales, dL_drotations, dL_dcov3D, *depth);
+  } else { GSR_PROF("preprocess_bwd_views", st);
     hipLaunchKernelGGL(preprocess_bwd_views_kernel, dim3((P + GSR_BLOCK - 1) / GSR_BLOCK), dim3(GSR_BLOCK), 0, st, vw, P,
                        scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity,
                        dL_dscales, dL_drotations, dL_dcov3D); }

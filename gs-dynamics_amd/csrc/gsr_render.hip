@@ -511,21 +511,38 @@ struct BwdLdsT {
 
 struct BwdPartner { const float4* rec; const float* bg; const float* dL_dcolor; };
 
+// Differentiable depth (DEPTH builds, plain passes only).  The depth image D = sum_i alpha_i T_i z_i is a fourth colour channel with colour
+// z_i and background 0: its incoming gradient dLd adds z * dLd to each entry's colour dot product (so dL/dalpha, and through it every
+// geometry partial, carries it), and each entry gets one more wave-reduced partial, dL/dz_i = sum over pixels of alpha T dLd.  That tenth
+// (or seventh) value lives outside the record: its own LDS (below, next to the regular layout) and its own [num_rendered] float array
+// (GsrDepthViews::dL_dz, indexed like the records).
+template <int NBB>
+struct BwdDepthLds {
+  float sZ[4][NBB + 1];     // per-strip compacted: the entry's view-space depth (staged next to sC)
+  float sRedZ[4][NBB];      // per-wave totals of alpha T dLd, by batch index
+};
+struct BwdDepth { const float* dL_ddepth; float* dL_dz; };
+
 // COL = false (plain passes only): the caller wants no colour gradient -- six sums per entry instead of nine (15 instead of 24
 // VALU issues of reduction, four multiplies less) and 24-byte records.
 // The no-colour reduction is the six-value one (gsr_wave_sum6_packed; its build must stay within the launch's register budget: round 2's
 // "six values are slower than nine with zeros" was a 97th VGPR, see render_bwd_persistent's launch bounds).
 #define GSR_NOCOL_REDUCE { const float z = gsr_wave_sum6_packed(tx, ty, tx * dx, tx * dy, ty * dy, v5); \
                            if (red6 >= 0) L.sRed[wv][j][red6] = z; }
+// DEPTH: dL/dz of the entry, summed over the wave; lane 63 parks the total
+#define GSR_BWD_PARK_Z(vz) { const float zt = gsr_wave_sum_to_lane63(vz); if (lane == 63) LZ->sRedZ[wv][j] = zt; }
 #define GSR_NOCOL_STORE6(p, e, r0, a, b) gsr_store_partial6(p, e, r0, a, b)   // (36-byte stores instead: measured the same)
 // BASE: the ticket's base wave priority (one-view launches: the longest tickets run at base 1 -- the longest lists of a short queue get a
 // larger share of their CU and finish with the pack instead of draining alone; see gsr_launch_render_bwd)
-template <bool PAIR, int NBB = GSR_BWD_BB(PAIR), bool COL = true, int BASE = 0>
+// DEPTH: the differentiable-depth build (see BwdDepthLds); LZ / dp are used by it alone.
+template <bool PAIR, int NBB = GSR_BWD_BB(PAIR), bool COL = true, int BASE = 0, bool DEPTH = false>
 __device__ __forceinline__ void bwd_tile(
     const int tile, const uint2 rg, BwdLdsT<PAIR, NBB>& L, int W, int H, int gx,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, const float* __restrict__ bg,
     const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dcolor,
-    float4* __restrict__ partials, const uint8_t* __restrict__ contrib, const uint8_t* __restrict__ used, const BwdPartner pt) {
+    float4* __restrict__ partials, const uint8_t* __restrict__ contrib, const uint8_t* __restrict__ used, const BwdPartner pt,
+    BwdDepthLds<NBB>* LZ = nullptr, const BwdDepth dp = BwdDepth{nullptr, nullptr}) {
+  static_assert(!(DEPTH && PAIR), "no fused-pair depth build");
   constexpr int BB = NBB;
   constexpr bool ROWS_PERM = !PAIR && NBB == BWD_BATCH;   // the short-queue build: see gsr_rows_sum
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -544,6 +561,8 @@ __device__ __forceinline__ void bwd_tile(
   const int last = inside ? (int)n_contrib[pix] : 0;
   float dL0 = 0.f, dL1 = 0.f, dL2 = 0.f;
   if (inside) { dL0 = dL_dcolor[pix]; dL1 = dL_dcolor[N + pix]; dL2 = dL_dcolor[2 * N + pix]; }
+  float dLd = 0.f;   // DEPTH: this pixel's dL/ddepth (depth has no background term: nTfbg is unchanged)
+  if (DEPTH && inside && dp.dL_ddepth) dLd = dp.dL_ddepth[pix];
   const float nTfbg = -T_final * (bg[0] * dL0 + bg[1] * dL1 + bg[2] * dL2);
   float T = T_final;
   // Colour accumulated behind the current entry, only ever used dotted with this pixel's dL/dcolour: kept as that dot
@@ -585,6 +604,7 @@ __device__ __forceinline__ void bwd_tile(
   // Software-pipelined staging (see fwd_tile): batch b+1 is fetched while batch b is processed.
   float4 na = make_float4(0.f, 0.f, 0.f, 0.f), nb = na;
   float nblue = 0.f;
+  float nz = 0.f;      // DEPTH: the entry's view-space depth
   float4 nslot = na;   // record word 3: rect bits, offsets[g]
   float4 np = na;      // PAIR: partner colour
   uint2 nbox = make_uint2(1u, 1u);
@@ -596,6 +616,7 @@ __device__ __forceinline__ void bwd_tile(
   if (fill0) slz = rec[GSR_REC_F4 * gz + 3];   // rect bits, offsets[g]
   if (tid < BB && tid < max_last) {
     { const float4 t2 = rec[GSR_REC_F4 * ng + 2]; na = rec[GSR_REC_F4 * ng]; nb = rec[GSR_REC_F4 * ng + 1]; nblue = t2.x;
+      if (DEPTH) nz = t2.y;
       nslot = rec[GSR_REC_F4 * ng + 3];
       nbox = make_uint2(__float_as_uint(t2.z), __float_as_uint(t2.w)); }
     if (PAIR) { const float4 q1 = pt.rec[GSR_REC_F4 * ng + 1]; np = make_float4(q1.z, q1.w, pt.rec[GSR_REC_F4 * ng + 2].x, 0.f); }
@@ -615,12 +636,14 @@ __device__ __forceinline__ void bwd_tile(
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     if (PAIR || COL) gsr_store_partial(partials, e, z, z, 0.f);
     else GSR_NOCOL_STORE6(partials, e, z, 0.f, 0.f);
+    if (DEPTH) dp.dL_dz[e] = 0.f;
   }
   GSR_TP(0);
   for (int base = 0; base < max_last; base += BB) {
     // batch entry j (0 = deepest still unprocessed) is list position pos = max_last - 1 - (base + j)
     const int m_all = min(BB, max_last - base);
     const float4 a = na, b = nb, d = np;
+    const float zc = nz;
     const float2 c = make_float2(nblue, __uint_as_float((uint32_t)tid));
     uint32_t mask = 0;
     if (tid < m_all) {
@@ -640,6 +663,7 @@ __device__ __forceinline__ void bwd_tile(
         nquads = contrib ? contrib[rg.x + (max_last - 1 - nj)] : 0xfu;
         if (nj + BB < max_last) ng_ahead = point_list[rg.x + (max_last - 1 - (nj + BB))];
         { const float4 t2 = rec[GSR_REC_F4 * ng + 2]; na = rec[GSR_REC_F4 * ng]; nb = rec[GSR_REC_F4 * ng + 1]; nblue = t2.x;
+      if (DEPTH) nz = t2.y;
       nslot = rec[GSR_REC_F4 * ng + 3];
       nbox = make_uint2(__float_as_uint(t2.z), __float_as_uint(t2.w)); }
         if (PAIR) { const float4 q1 = pt.rec[GSR_REC_F4 * ng + 1]; np = make_float4(q1.z, q1.w, pt.rec[GSR_REC_F4 * ng + 2].x, 0.f); }
@@ -664,6 +688,7 @@ __device__ __forceinline__ void bwd_tile(
         L.sB[w][p] = make_float4(GSR_STAGE_A(b.x), b.y, b.z, b.w);               // -C/2
         L.sC[w][p] = c;
         if (PAIR) L.sD[w][p] = d;
+        if (DEPTH) LZ->sZ[w][p] = zc;
       }
     }
 #ifdef GSR_ABL_NOVISIT   // ablation build (tools/r05_ablation.sh): the replay loop walks nothing -- what is left is staging, barriers, combine and stores
@@ -677,13 +702,14 @@ __device__ __forceinline__ void bwd_tile(
     const float4* __restrict__ wB = L.sB[wv];
     const float2* __restrict__ wC = L.sC[wv];
     const float4* __restrict__ wD = L.sD[wv];
+    const float* __restrict__ wZ = DEPTH ? LZ->sZ[wv] : nullptr;
     // One list entry: re-evaluate alpha; when some pixel of the quad used the entry, back out T, form the nine partials,
     // reduce them over the wave and park the totals.
 #ifndef GSR_PRIO_VISIT
 #define GSR_PRIO_VISIT 1      /* wave priority (s_setprio) of the replay loop; 0 = leave it alone.  Measured, 8 views, one box, 3 rounds each:
                                  0: 441.7 us, 1 / 2 / 3: 433.6 / 431.9 / 431.9 us per launch; raising the staging phase as well or instead: 437.8 / 448 */
 #endif
-#define GSR_BWD_ENTRY(ea, eb, ec, ed)                                                                           \
+#define GSR_BWD_ENTRY(ea, eb, ec, ed, ez)                                                                       \
     {                                                                                                         \
       const int j = __builtin_amdgcn_readfirstlane((int)__float_as_uint(ec.y)); /* batch index, wave-uniform */ \
       const int pos = max_last - 1 - (base + j);                                                              \
@@ -703,7 +729,8 @@ __device__ __forceinline__ void bwd_tile(
         const float rcp = __builtin_amdgcn_rcpf(1.0f - alpha);                                                \
         T = T * rcp;                                                                                          \
         acc_dot = __builtin_fmaf(last_alpha, last_cdot - acc_dot, acc_dot);                                   \
-        const float cdot = __builtin_fmaf(blue, dL2, __builtin_fmaf(eb.w, dL1, eb.z * dL0));                  \
+        float cdot = __builtin_fmaf(blue, dL2, __builtin_fmaf(eb.w, dL1, eb.z * dL0));                        \
+        if (DEPTH) cdot = __builtin_fmaf(ez, dLd, cdot);   /* the depth channel: colour z, gradient dLd */       \
         last_cdot = cdot;                                                                                     \
         float dL_dalpha = cdot - acc_dot;                                                                     \
         dL_dalpha = __builtin_fmaf(dL_dalpha, T, nTfbg * rcp);                                                \
@@ -726,6 +753,7 @@ __device__ __forceinline__ void bwd_tile(
           const float t = eb.y * v5;                                                                          \
           const float tx = t * dx, ty = t * dy;                                                               \
           GSR_NOCOL_REDUCE                                                                                    \
+          if (DEPTH) GSR_BWD_PARK_Z((alpha * T) * dLd)                                                        \
         } else {                                                                                              \
         last_alpha = alpha;                                                                                   \
         const float w = alpha * T;                                                                            \
@@ -740,6 +768,7 @@ __device__ __forceinline__ void bwd_tile(
         const float v2 = tx * dx, v3 = tx * dy, v4 = ty * dy;                                                 \
         const float v6 = w * dL0, v7 = w * dL1, v8 = w * dL2;                                                 \
         GSR_BWD_PARK9(v0, v1, v2, v3, v4, v5, v6, v7, v8)                                                     \
+        if (DEPTH) GSR_BWD_PARK_Z(w * dLd)                                                                    \
         }                                                                                                     \
       }                                                                                                       \
     }
@@ -749,17 +778,20 @@ __device__ __forceinline__ void bwd_tile(
     float4 ea = wA[0], eb = wB[0];
     float2 ec = wC[0];
     float4 ed = wD[0];
+    float ez = DEPTH ? wZ[0] : 0.f;
     int jj = 0;
     for (; jj + 1 < m; jj += 2) {
       const float4 xa = wA[jj + 1], xb = wB[jj + 1];
       const float2 xc = wC[jj + 1];
       const float4 xd = PAIR ? wD[jj + 1] : ed;
-      GSR_BWD_ENTRY(ea, eb, ec, ed)
+      const float xz = DEPTH ? wZ[jj + 1] : 0.f;
+      GSR_BWD_ENTRY(ea, eb, ec, ed, ez)
       ea = wA[jj + 2]; eb = wB[jj + 2]; ec = wC[jj + 2];
       if (PAIR) ed = wD[jj + 2];
-      GSR_BWD_ENTRY(xa, xb, xc, xd)
+      if (DEPTH) ez = wZ[jj + 2];
+      GSR_BWD_ENTRY(xa, xb, xc, xd, xz)
     }
-    if (jj < m) GSR_BWD_ENTRY(ea, eb, ec, ed)
+    if (jj < m) GSR_BWD_ENTRY(ea, eb, ec, ed, ez)
 #undef GSR_BWD_ENTRY
     if (GSR_PRIO_VISIT) __builtin_amdgcn_s_setprio(BASE);
     GSR_TP(4);
@@ -781,6 +813,13 @@ __device__ __forceinline__ void bwd_tile(
       const uint32_t e = L.sSlot[tid];
       if (PAIR || COL) gsr_store_partial(partials, e, r0, r1, r2.x);
       else GSR_NOCOL_STORE6(partials, e, r0, r1.x, r1.y);
+      if (DEPTH) {   // same quads, same order of additions as the record's sums
+        float rz = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          if ((quads >> w) & 1u) rz += LZ->sRedZ[w][tid];
+        dp.dL_dz[e] = rz;
+      }
     }
     GSR_TP(6);
     __syncthreads();
@@ -933,6 +972,42 @@ __global__ __launch_bounds__(GSR_BLOCK, (!PAIRS && NBB == BWD_SMALL_BB) ? BWD_SM
   // The last workgroup to leave re-arms the queue for a possible second backward over the same state
   // (retain_graph): no workgroup can still be popping once all of them have checked out.  Saves a memset launch.
   if (threadIdx.x == 0 && atomicAdd(&queue[5], 1u) == gridDim.x - 1u) {
+    atomicExch(&queue[1], 0u);
+    atomicExch(&queue[5], 0u);
+  }
+}
+// The differentiable-depth backward (gsr_backward_depth / gsr_backward_batch_depth): the plain persistent pass with the depth channel.
+// Always the 80-entry batch: its LDS plus the depth arrays (27.5 KB) still fits five workgroups per CU, which is what the launch asks
+// for; the launch bounds hold it to that residency (<= 96 VGPRs -- kernel-resource-usage reports the count).  No pair build, no
+// producer / consumer form.
+#define BWD_DEPTH_BB BWD_SMALL_BB
+#define BWD_DEPTH_WAVES 5
+// The ticket loop is render_bwd_persistent's (plain tickets only; the existing kernels keep their own text so that their code is unchanged).
+template <bool COL>
+__global__ __launch_bounds__(GSR_BLOCK, BWD_DEPTH_WAVES) void render_bwd_persistent_depth(GsrRenderViews tab, GsrDepthViews dv) {
+  constexpr int NBB = BWD_DEPTH_BB;
+  __shared__ BwdLdsT<false, NBB> L;
+  __shared__ BwdDepthLds<NBB> LZ;
+  __shared__ uint32_t s_ticket;
+  const uint4* __restrict__ tile_order = tab.order;
+  uint32_t* __restrict__ queue = tab.queue;
+  const uint32_t n_busy = queue[4];
+  uint32_t ticket = blockIdx.x;
+  while (ticket < n_busy) {
+    const uint4 ord = tile_order[ticket];
+    const uint32_t vi = __builtin_amdgcn_readfirstlane(ord.w);
+    const GsrRenderView& vw = tab.v[vi];
+    const BwdDepth dp{dv.dL_ddepth[vi], dv.dL_dz[vi]};
+    if (ticket * 256u < n_busy * (uint32_t)tab.prio_frac256)
+      bwd_tile<false, NBB, COL, 1, true>((int)ord.x, make_uint2(ord.y, ord.z), L, GSR_BWD_PASS(vw), BwdPartner{}, &LZ, dp);
+    else
+      bwd_tile<false, NBB, COL, 0, true>((int)ord.x, make_uint2(ord.y, ord.z), L, GSR_BWD_PASS(vw), BwdPartner{}, &LZ, dp);
+    if (threadIdx.x == 0) s_ticket = gridDim.x + atomicAdd(&queue[1], 1u);
+    __syncthreads();
+    ticket = s_ticket;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && atomicAdd(&queue[5], 1u) == gridDim.x - 1u) {   // re-arm the queue (see render_bwd_persistent)
     atomicExch(&queue[1], 0u);
     atomicExch(&queue[5], 0u);
   }
@@ -1517,9 +1592,21 @@ int gsr_launch_render_fwd(const GsrRenderViews& tab, hipStream_t st) {
   return 0;
 }
 
-int gsr_launch_render_bwd(const GsrRenderViews& tab_in, hipStream_t st) {
+int gsr_launch_render_bwd(const GsrRenderViews& tab_in, hipStream_t st, const GsrDepthViews* depth) {
   if (tab_in.T <= 0 || tab_in.V <= 0) return 0;
   GsrRenderViews tab = tab_in;
+  if (depth) {   // differentiable depth: the plain persistent pass only (the caller unfused any pairs)
+    if (has_pairs(tab)) { gsr_set_error("render_bwd: the depth build takes no fused pairs"); return -2; }
+    tab.prio_frac256 = tab.V <= 1 ? 160 : (tab.V >= 3 ? 192 : 0);   // (as below)
+    tab.pc_error_out = nullptr;
+    const int tiles = tab.T * tab.V;
+    const int grid = tiles < 256 * BWD_DEPTH_WAVES ? tiles : 256 * BWD_DEPTH_WAVES;
+    { GSR_PROF("render_bwd_depth", st);
+      if (tab.no_colour_grad) hipLaunchKernelGGL(render_bwd_persistent_depth<false>, dim3(grid), dim3(GSR_BLOCK), 0, st, tab, *depth);
+      else hipLaunchKernelGGL(render_bwd_persistent_depth<true>, dim3(grid), dim3(GSR_BLOCK), 0, st, tab, *depth); }
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   // Base wave priority of a ticket (round 4).  One view per launch -- the per-GPU share of a view-sharded step -- is ONE round of tickets
   // on the resident workgroups followed by a drain in which they finish one by one: the longest 10/16 of the tickets (the order is
   // longest-first: rank = ticket) run at base priority 1, so that a CU's long lists get a larger share of it and end with the pack:

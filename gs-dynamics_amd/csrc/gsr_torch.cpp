@@ -269,7 +269,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, double tan_fovx, double tan_fovy,
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                             bool want_color_grad) {   // extension over upstream (default true): false = colours_precomp needs no gradient
+                             bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
+                             const c10::optional<torch::Tensor>& dL_dout_depth) {   // extension (default None): [1, H, W] -> gsr_backward_depth
   const c10::Device dev = means3D.device();
   c10::hip::HIPGuard guard(dev.index());
   const int64_t P = means3D.size(0);
@@ -299,10 +300,23 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   const torch::Tensor m3 = f32c(means3D, dev), col = f32c(colors, dev), sc = f32c(scales, dev), rot = f32c(rotations, dev),
                       cov = f32c(cov3D_precomp, dev), shs = f32c(sh, dev), g = f32c(dL_dout_color, dev);
   Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev);
-  torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R)},
-                                       torch::TensorOptions().dtype(torch::kUInt8).device(dev));
   void* stream = (void*)c10::hip::getCurrentHIPStream(dev.index()).stream();
   auto optr = [](torch::Tensor& t) -> float* { return t.numel() ? t.data_ptr<float>() : nullptr; };
+  if (dL_dout_depth.has_value() && dL_dout_depth->defined()) {   // differentiable depth: the depth build, its larger scratch
+    TORCH_CHECK(dL_dout_depth->numel() == H * W, "dL_dout_depth must hold H * W elements ([1, H, W])");
+    const torch::Tensor gd = f32c(*dL_dout_depth, dev);
+    torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)},
+                                         torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    check(gsr_backward_depth(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                             radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                             g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                             optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
+                             gd.data_ptr<float>(), stream),
+          "gsr_backward_depth");
+    return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
+  }
+  torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R)},
+                                       torch::TensorOptions().dtype(torch::kUInt8).device(dev));
   check(gsr_backward(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov), radii.data_ptr<int32_t>(),
                      geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(), g.data_ptr<float>(),
                      R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(), optr(d_colors),
@@ -322,9 +336,11 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                                 torch::Tensor sh, torch::Tensor colors, torch::Tensor opacities, torch::Tensor scales,
                                                 torch::Tensor rotations, torch::Tensor cov3D, torch::Tensor bg, torch::Tensor viewmatrix,
                                                 torch::Tensor projmatrix, torch::Tensor campos, double tanfovx, double tanfovy, int64_t H,
-                                                int64_t W, double scale_modifier, int64_t degree, bool prefiltered, bool will_backward) {
+                                                int64_t W, double scale_modifier, int64_t degree, bool prefiltered, bool will_backward,
+                                                bool differentiable_depth) {
     (void)means2D;
-    ctx->set_materialize_grads(false);        // grad_depth is ignored: do not let autograd fill a zero image for it
+    ctx->set_materialize_grads(false);        // grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it
+    ctx->saved_data["depth"] = differentiable_depth;
     Forward r = rasterize_forward(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tanfovx,
                                   tanfovy, H, W, sh, degree, campos, prefiltered, will_backward, true, t_call_state);
     torch::Tensor color = r.color, depth = r.depth, radii = r.radii;
@@ -339,20 +355,23 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     return {color, radii, depth};
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    torch::autograd::variable_list out(20);       // one slot per forward argument; undefined = no gradient
+    torch::autograd::variable_list out(21);       // one slot per forward argument; undefined = no gradient
     if (ctx->saved_data["empty"].toBool()) return out;
     const auto sv = ctx->get_saved_variables();
     const torch::Tensor &m3 = sv[0], &radii = sv[1], &col = sv[2], &sh = sv[3], &sc = sv[4], &rot = sv[5], &cov = sv[6], &geom = sv[7],
                         &binning = sv[8], &image = sv[9], &bg = sv[10], &view = sv[11], &proj = sv[12], &campos = sv[13];
     const int64_t H = ctx->saved_data["H"].toInt(), W = ctx->saved_data["W"].toInt();
-    torch::Tensor g = grads[0];                   // grads[1] (radii), grads[2] (depth): accepted, ignored -- no reference call site differentiates them
+    torch::Tensor g = grads[0];                   // grads[1] (radii): accepted, ignored -- no reference call site differentiates it
+    // grads[2] (depth): ignored unless the call opted in (differentiable_depth); then the depth build -- when autograd delivers one
+    c10::optional<torch::Tensor> gd;
+    if (ctx->saved_data["depth"].toBool() && grads[2].defined()) gd = grads[2];
     if (!g.defined()) g = torch::zeros({3, H, W}, m3.options().dtype(torch::kFloat32));
     const bool has_sh = ctx->saved_data["has_sh"].toBool(), has_col = ctx->saved_data["has_col"].toBool(),
                has_sc = ctx->saved_data["has_sc"].toBool(), has_cov = ctx->saved_data["has_cov"].toBool();
     const bool want_col = has_col && ctx->needs_input_grad(3);      // frozen colours (the reference's training): the six-sum backward
     auto r = rasterize_gaussians_backward(bg, m3, radii, col, sc, rot, ctx->saved_data["scale_modifier"].toDouble(), cov, view, proj,
                                           ctx->saved_data["tanfovx"].toDouble(), ctx->saved_data["tanfovy"].toDouble(), g, sh,
-                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col);
+                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd);
     out[0] = std::get<3>(r);                      // means3D
     out[1] = std::get<0>(r);                      // means2D (x, y in NDC units, z = 0)
     if (has_sh) out[2] = std::get<5>(r);
@@ -372,7 +391,8 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
           const torch::Tensor& means3D, const torch::Tensor& means2D, const torch::Tensor& sh, const torch::Tensor& colors,
           const torch::Tensor& opacities, const torch::Tensor& scales, const torch::Tensor& rotations, const torch::Tensor& cov3D,
           const torch::Tensor& bg, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& campos,
-          double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered) {
+          double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered,
+          bool differentiable_depth) {   // extension: the depth output is differentiated too (gsr_backward_depth)
   bool will_backward = false;
   if (at::GradMode::is_enabled())
     for (const torch::Tensor* t : {&means3D, &means2D, &sh, &colors, &opacities, &scales, &rotations, &cov3D})
@@ -383,7 +403,7 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
     ~Scope() { t_call_state = prev; }
   } scope(state.get());
   auto o = RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos, tanfovx,
-                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward);
+                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth);
   return std::make_tuple(o[0], o[1], o[2]);
 }
 
@@ -431,8 +451,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"),
         py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"),
         py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"),
-        py::arg("want_color_grad") = true);
-  m.def("rasterize", &rasterize);      // one GaussianRasterizer call: forward + the autograd node (C++); first argument: the LayerState or None
+        py::arg("want_color_grad") = true, py::arg("dL_dout_depth") = py::none());
+  // one GaussianRasterizer call: forward + the autograd node (C++); first argument: the LayerState or None
+  m.def("rasterize", &rasterize, py::arg("state"), py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"), py::arg("opacities"),
+        py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"),
+        py::arg("tanfovx"), py::arg("tanfovy"), py::arg("H"), py::arg("W"), py::arg("scale_modifier"), py::arg("degree"), py::arg("prefiltered"),
+        py::arg("differentiable_depth") = false);
   m.def("mark_visible", &mark_visible);
   m.def("abi_version", []() { return (int)GSR_VERSION; });   // the header this layer was COMPILED against (compare with the library's gsr_version())
 }

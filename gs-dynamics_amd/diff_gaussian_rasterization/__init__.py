@@ -99,8 +99,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
-        ctx.set_materialize_grads(False)  # grad_depth is ignored: do not let autograd fill a zero image for it
+                raster_settings, differentiable_depth=False):
+        # grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it (or for an unused colour)
+        ctx.set_materialize_grads(False)
+        ctx.depth = bool(differentiable_depth)
         m3 = _prep(means3D)
         if m3 is None:
             if means3D is not None and means3D.dim() == 2 and means3D.shape[1] == 3:
@@ -143,9 +145,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth):  # grad_radii / grad_depth: accepted, ignored
+    def backward(ctx, grad_color, grad_radii, grad_depth):  # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth
         if ctx.empty:
-            return (None,) * 9
+            return (None,) * 10
+        if not ctx.depth:
+            grad_depth = None
         if ctx.native is not None:
             m3, radii, col_, sh_, sc_, rot_, cov_, geom, binning, image = ctx.saved_tensors
             has_sh, has_col, has_sc, has_cov = ctx.has
@@ -155,9 +159,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             d2, dc, do, d3, dcov, dsh, ds, dr = ctx.native.rasterize_gaussians_backward(
                 rs.bg, m3, radii, col_, sc_, rot_, float(rs.scale_modifier), cov_, rs.viewmatrix, rs.projmatrix, float(rs.tanfovx),
                 float(rs.tanfovy), grad_color, sh_, int(rs.sh_degree), rs.campos, geom, ctx.num_rendered, binning, image,
-                bool(has_col and ctx.needs_input_grad[3]))   # frozen colours (the reference's training): the six-sum backward
+                bool(has_col and ctx.needs_input_grad[3]),   # frozen colours (the reference's training): the six-sum backward
+                *(() if grad_depth is None else (grad_depth,)))
             return (d3, d2, dsh if has_sh else None, dc if (has_col and ctx.needs_input_grad[3]) else None, do, ds if has_sc else None, dr if has_sc else None,
-                    dcov if has_cov else None, None)
+                    dcov if has_cov else None, None, None)
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         if grad_color is None:
@@ -165,9 +170,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh = _hip.rasterize_backward(
             ctx.state, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
-            want_color_grad=bool(has_col and ctx.needs_input_grad[3]))
+            want_color_grad=bool(has_col and ctx.needs_input_grad[3]), **({} if grad_depth is None else {"grad_depth": grad_depth}))
         return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity,
-                d_scales if has_sc else None, d_rot if has_sc else None, d_cov if has_cov else None, None)
+                d_scales if has_sc else None, d_rot if has_sc else None, d_cov if has_cov else None, None, None)
 
 
 class _RasterizeGaussiansViews(torch.autograd.Function):
@@ -177,8 +182,10 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
     (densification accumulates their norms per view, /root/reference/src/tracking/external.py:138-142)."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
+                differentiable_depth=False):
         ctx.set_materialize_grads(False)
+        ctx.depth = bool(differentiable_depth)
         m3 = _prep(means3D)
         if m3 is None or m3.dim() != 2 or m3.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -186,7 +193,8 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         sc_, rot_, cov_ = _prep(scales), _prep(rotations), _prep(cov3Ds_precomp)
         wants_grad = any(ctx.needs_input_grad)
         color, radii, depth, states = _hip.rasterize_forward_batch(list(settings_list), m3, op_, col_, sh_, sc_, rot_, cov_,
-                                                                   prepare_backward=wants_grad, **({} if wants_grad else {"forward_only": True}))
+                                                                   prepare_backward=wants_grad, **({} if wants_grad else {"forward_only": True}),
+                                                                   **({"depth_scratch": True} if (ctx.depth and wants_grad) else {}))
         ctx.states = states
         ctx.has = (sh_ is not None, col_ is not None, sc_ is not None, cov_ is not None)
         empty = m3.new_empty(0)
@@ -206,16 +214,19 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         d3, d2, dc, do, ds, dr, dcov, dsh = _hip.rasterize_backward_batch(
             ctx.states, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
-            want_color_grad=bool(has_col and ctx.needs_input_grad[3]))
+            want_color_grad=bool(has_col and ctx.needs_input_grad[3]),
+            **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}))
         # gradients arrive already summed over views (means2D stays per view); the state stays on ctx so that a
         # second backward (retain_graph=True) works, and is released with the graph
         return (d3, d2, dsh if has_sh else None, dc if has_col else None, do, ds if has_sc else None,
-                dr if has_sc else None, dcov if has_cov else None, None)
+                dr if has_sc else None, dcov if has_cov else None, None, None)
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None):
-    """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder."""
+                              rotations=None, cov3D_precomp=None, differentiable_depth=False):
+    """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder.
+    ``differentiable_depth``: the depth output [V,1,H,W] is differentiated too (see GaussianRasterizer); views that share a camera,
+    which the backward otherwise fuses into one pass, are then differentiated unfused."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -234,7 +245,7 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
             means3D, means2D if whole else means2D[lo:hi], empty if shs is None else shs,
             empty if colors_precomp is None else (colors_precomp[lo:hi] if (per_view_col and not whole) else colors_precomp), opacities,
             empty if scales is None else scales, empty if rotations is None else rotations,
-            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi])
+            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth))
     if V <= _hip.MAX_BATCH:
         return call(0, V)
     # more views than one library call takes: several calls, outputs concatenated (autograd sums the shared inputs)
@@ -243,25 +254,34 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, differentiable_depth=False):
     native = _native() if (means3D is not None and means3D.is_cuda) else None
     if native is not None and hasattr(native, "rasterize") and not _PY_NODE:
         # one crossing into the torch C++ layer: forward and the autograd node live there (csrc/gsr_torch.cpp: RasterizeFn)
         rs = raster_settings
         return native.rasterize(layer_state(means3D.device), means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg, rs.viewmatrix,
                                 rs.projmatrix, rs.campos, float(rs.tanfovx), float(rs.tanfovy), int(rs.image_height), int(rs.image_width),
-                                float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered))
+                                float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered),
+                                *((True,) if differentiable_depth else ()))
+    if differentiable_depth:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings)
 
 
 class GaussianRasterizer(nn.Module):
     """Constructed per call by the reference (``Renderer(raster_settings=cam)(**rendervar)``,
-    /root/reference/src/tracking/train_utils.py:178): construction does no work."""
+    /root/reference/src/tracking/train_utils.py:178): construction does no work.
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings):
+    ``differentiable_depth`` (extension, default False): the depth output is differentiated too.  D = sum_i alpha_i T_i z_i (z_i: the
+    Gaussian's view-space depth, no background term) is treated as a fourth colour channel with colour z_i and background 0, plus
+    z_i -> means3D; the depth term reaches every input gradient through dL/dalpha.  False: the depth gradient is ignored, as upstream."""
+
+    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False):
         super().__init__()
         self.raster_settings = raster_settings
+        self.differentiable_depth = bool(differentiable_depth)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -284,5 +304,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        if self.differentiable_depth:
+            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                       cov3D_precomp, rs, differentiable_depth=True)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)

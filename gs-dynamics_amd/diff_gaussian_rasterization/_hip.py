@@ -70,7 +70,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_mark_visible", "gsr_debug_get_views", "gsr_selftest", "gsr_profile_begin", "gsr_profile_end",
            "gsr_batch_state_bytes", "gsr_forward_preprocess_batch", "gsr_forward_render_batch", "gsr_forward_batch",
            "gsr_forward_batch_capacity", "gsr_forward_batch_capacity_raw",
-           "gsr_backward_batch", "gsr_backward_batch_raw", "gsr_debug_phase_timing",
+           "gsr_backward_batch", "gsr_backward_batch_raw", "gsr_backward_depth", "gsr_backward_batch_depth",
+           "gsr_backward_scratch_bytes_depth", "gsr_debug_phase_timing",
            "gsr_image_loss_blocks", "gsr_image_loss_forward", "gsr_image_loss_backward", "gsr_fps", "gsr_fps_scratch_bytes", "gsr_fit_rotations", "gsr_fit_bones", "gsr_fps_thin", "gsr_construct_edges", "gsr_lbs_valid", "gsr_lbs",
            "gsr_rigidity_blocks", "gsr_rigidity_forward", "gsr_rigidity_backward",
            "gsr_views_loss_blocks", "gsr_views_loss_forward", "gsr_views_loss_backward", "gsr_target_moments",
@@ -98,12 +99,15 @@ def load_library():
     lib.gsr_image_bytes.restype = sz; lib.gsr_image_bytes.argtypes = [i32, i32]
     lib.gsr_binning_bytes.restype = sz; lib.gsr_binning_bytes.argtypes = [u32, i32, i32]
     lib.gsr_backward_scratch_bytes.restype = sz; lib.gsr_backward_scratch_bytes.argtypes = [i32, u32]
+    lib.gsr_backward_scratch_bytes_depth.restype = sz; lib.gsr_backward_scratch_bytes_depth.argtypes = [i32, u32]
     lib.gsr_forward_preprocess.restype = C.c_int
     lib.gsr_forward_preprocess.argtypes = [C.POINTER(GsrSettings), i32] + [vp] * 7 + [vp, vp, C.POINTER(u32), vp]
     lib.gsr_forward_render.restype = C.c_int
     lib.gsr_forward_render.argtypes = [C.POINTER(GsrSettings), i32, u32, vp, vp, vp, vp, vp, vp]
     lib.gsr_backward.restype = C.c_int
     lib.gsr_backward.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 20 + [vp]
+    lib.gsr_backward_depth.restype = C.c_int
+    lib.gsr_backward_depth.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 21 + [vp]
     PS = C.POINTER(GsrSettings)
     PV = C.POINTER(C.c_void_p)
     lib.gsr_batch_state_bytes.restype = sz; lib.gsr_batch_state_bytes.argtypes = [i32, i32, i32, i32]
@@ -124,6 +128,8 @@ def load_library():
     lib.gsr_forward_batch_capacity_raw.argtypes = lib.gsr_forward_batch_capacity.argtypes[:-1] + [C.POINTER(GsrRawParams), vp]
     lib.gsr_backward_batch_raw.restype = C.c_int
     lib.gsr_backward_batch_raw.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [C.POINTER(GsrRawParams), vp]
+    lib.gsr_backward_batch_depth.restype = C.c_int
+    lib.gsr_backward_batch_depth.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, vp]
     lib.gsr_image_loss_blocks.restype = i32
     lib.gsr_image_loss_blocks.argtypes = [i32, i32, i32]
     lib.gsr_image_loss_forward.restype = C.c_int
@@ -353,10 +359,11 @@ def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotat
 
 
 def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_precomp, shs, scales, rotations,
-                       cov3D_precomp, want_color_grad: bool = True):
+                       cov3D_precomp, want_color_grad: bool = True, grad_depth=None):
     """K7..K9.  Returns (dmeans3D, dmeans2D, dcolors, dopacity[P,1], dscales, drotations, dcov3D, dsh).
     ``want_color_grad=False`` (precomputed colours that need no gradient): dcolors is None and the blend backward keeps six sums
-    per list entry instead of nine."""
+    per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (gsr_backward_depth); None is
+    exactly gsr_backward."""
     lib = load_library()
     dev = means3D.device
     P, D = state.P, state.num_rendered
@@ -372,6 +379,17 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
         d_rot = torch.empty((P, 4), **f32) if cov3D_precomp is None else None
         d_cov = torch.empty((P, 6), **f32)
         d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
+        if grad_depth is not None:
+            gd = grad_depth.to(**f32).contiguous()
+            if gd.numel() != state.H * state.W:
+                raise ValueError(f"rasterize_backward: grad_depth must hold H * W = {state.H * state.W} elements ([1, H, W]), got {gd.numel()}")
+            scratch = torch.empty((lib.gsr_backward_scratch_bytes_depth(P, D),), dtype=torch.uint8, device=dev)
+            _check(lib.gsr_backward_depth(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                          _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
+                                          _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
+                                          _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
+                                          _ptr(d_cov), _ptr(d_sh), _ptr(gd), _stream(dev)), "gsr_backward_depth")
+            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
         scratch = torch.empty((lib.gsr_backward_scratch_bytes(P, D),), dtype=torch.uint8, device=dev)
         _check(lib.gsr_backward(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
                                 _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
@@ -428,10 +446,12 @@ FORWARD_ONLY = 1        # GSR_FORWARD_ONLY of include/gsr.h
 
 def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, shs, scales, rotations, cov3D_precomp,
                             prepare_backward: bool = False, no_host_sync: bool = False, raw=None, forward_only: bool = False,
-                            grad_out=None, depth_cuts=None):
+                            grad_out=None, depth_cuts=None, depth_scratch: bool = False):
     """All views of a step in one call: one launch per stage for all views, one host sync for all duplicate counts.  Returns (color[V,3,H,W], radii[V,P] int32, depth[V,1,H,W], states[V]).
     ``depth_cuts = (cut_in, cut_out, redo[, margin = 1.01])`` (forward_only calls; include/gsr.h: gsr_arm_depth_cuts): per view a [T] int32 tensor of depth
     bits to bin with (or None), a [T] int32 tensor that receives the next frame's proposal, and one zeroed [V] int32 tensor of redo flags.
+    ``depth_scratch``: the backward that follows will take a depth gradient -- the pre-allocated scratch is sized for it
+    (gsr_backward_scratch_bytes_depth).
     ``raw = (unnorm_rotations, logit_opacities, log_scales)`` (then ``opacities`` / ``scales`` / ``rotations`` are None): the
     activations are applied inside the preprocess kernel when the call runs in capacity mode (``states[0].raw_fused``), by
     ``activate_forward`` otherwise; either way ``states[0].act = (rotations, opacities, scales)`` holds the activated tensors."""
@@ -500,7 +520,8 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
             binnings = [torch.empty((bbytes,), **u8) if owner[v] else None for v in range(V)]
             pre = None
             if prepare_backward:
-                pre = _alloc_backward(dev, V, P, [int(lib.gsr_backward_scratch_bytes(P, cap_e))] * V, cov3D_precomp is None,
+                sbytes = lib.gsr_backward_scratch_bytes_depth if depth_scratch else lib.gsr_backward_scratch_bytes
+                pre = _alloc_backward(dev, V, P, [int(sbytes(P, cap_e))] * V, cov3D_precomp is None,
                                       colors_precomp is not None and colors_precomp.dim() == 3, grad_out)
             color_v, depth_v = [color[v] for v in range(V)], [depth[v] for v in range(V)]
             per_view_col = colors_precomp is not None and colors_precomp.dim() == 3
@@ -560,7 +581,8 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
         caps = (C.c_size_t * V)(*([cap] * V))
         pre = None
         if prepare_backward and cap and shs is None:   # scratch sized like the binning buffers: from the last call
-            pre = _alloc_backward(dev, V, P, [_scratch_capacity.get(key, 0)] * V, cov3D_precomp is None,
+            pre = _alloc_backward(dev, V, P, [int(lib.gsr_backward_scratch_bytes_depth(P, _entries_capacity.get(key, 0)))
+                                              if depth_scratch else _scratch_capacity.get(key, 0)] * V, cov3D_precomp is None,
                                   colors_precomp is not None and colors_precomp.dim() == 3, grad_out)
         color_v, depth_v = [color[v] for v in range(V)], [depth[v] for v in range(V)]
         per_view_col = colors_precomp is not None and colors_precomp.dim() == 3   # [V,P,3]: every view its own colours
@@ -609,7 +631,8 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
         if rc == 1 or need * 2 < cap:
             _binning_capacity[key] = int(need * _BINNING_SLACK)
             _scratch_capacity[key] = int(max(lib.gsr_backward_scratch_bytes(P, Ds[v]) for v in range(V)) * _BINNING_SLACK)
-        if pre is not None and any(lib.gsr_backward_scratch_bytes(P, Ds[v]) > pre["scratch"][v].numel() for v in range(V)):
+        sbytes = lib.gsr_backward_scratch_bytes_depth if depth_scratch else lib.gsr_backward_scratch_bytes
+        if pre is not None and any(sbytes(P, Ds[v]) > pre["scratch"][v].numel() for v in range(V)):
             pre = None
     states = []
     for v in range(V):
@@ -669,9 +692,12 @@ def forward_counts_ok(states) -> bool:
 
 
 def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp, shs, scales, rotations, cov3D_precomp,
-                             want_color_grad: bool = True, grad_out=None):
+                             want_color_grad: bool = True, grad_out=None, grad_depth=None):
     """Backward of all views.  Returns gradients already SUMMED over views (dmeans3D[P,3], dcolors, dopacity[P,1],
-    dscales, drotations, dcov3D, dsh) plus the per-view means2D gradients [V,P,3]."""
+    dscales, drotations, dcov3D, dsh) plus the per-view means2D gradients [V,P,3].
+    ``grad_depth`` ([V,1,H,W], or a sequence of V such images or None, or None): the depth images' gradient (gsr_backward_batch_depth:
+    views the forward fused into pairs are differentiated unfused; a None entry = no depth gradient for that view); None, or no image
+    at all, is exactly gsr_backward_batch."""
     lib = load_library()
     dev = means3D.device
     V = len(states)
@@ -679,8 +705,14 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     if states[0].forward_only:
         raise RuntimeError("rasterize_backward_batch: these states come from a forward_only forward (no record-slot offsets were produced)")
     f32 = dict(dtype=torch.float32, device=dev)
+    if grad_depth is not None and not isinstance(grad_depth, torch.Tensor):
+        if len(grad_depth) != V:
+            raise ValueError(f"rasterize_backward_batch: grad_depth must have one entry per view ({V})")
+        if all(d is None for d in grad_depth):
+            grad_depth = None
     if shs is not None:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
-        outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp)
+        outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp,
+                                   grad_depth=None if grad_depth is None else grad_depth[v])
                 for v in range(V)]
         sm = lambda k: None if outs[0][k] is None else torch.stack([o[k] for o in outs]).sum(0)  # noqa: E731
         return sm(0), torch.stack([o[1] for o in outs]), None, sm(3), sm(4), sm(5), sm(6), sm(7)
@@ -693,9 +725,21 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             Ds[v] = stt.num_rendered
         per_view_col = colors_precomp is not None and colors_precomp.dim() == 3
         pre, states[0].pre = states[0].pre, None   # one use only: autograd may keep the returned tensors as .grad
+        # the depth build's scratch: the records, then one float of dL/dz per entry (a forward told so -- depth_scratch -- sized it already)
+        sbytes = lib.gsr_backward_scratch_bytes_depth if grad_depth is not None else lib.gsr_backward_scratch_bytes
         if pre is None:
-            pre = _alloc_backward(dev, V, P, [lib.gsr_backward_scratch_bytes(P, stt.num_rendered) for stt in states],
-                                  cov3D_precomp is None, per_view_col, grad_out)
+            pre = _alloc_backward(dev, V, P, [sbytes(P, stt.num_rendered) for stt in states], cov3D_precomp is None, per_view_col, grad_out)
+        if grad_depth is not None:
+            if states[0].raw_fused is not None:
+                raise RuntimeError("rasterize_backward_batch: grad_depth is not supported with the fused raw-parameter activations")
+            HW = states[0].H * states[0].W
+            if isinstance(grad_depth, torch.Tensor):
+                grad_depth = [grad_depth[v] for v in range(V)]
+            gd = [None if d is None else d.to(**f32).contiguous() for d in grad_depth]
+            if any(d is not None and d.numel() != HW for d in gd):
+                raise ValueError(f"rasterize_backward_batch: every grad_depth image must hold H * W = {HW} elements")
+            pre["scratch"] = [s if s.numel() >= sbytes(P, stt.num_rendered) else torch.empty((sbytes(P, stt.num_rendered),), dtype=torch.uint8, device=dev)
+                              for s, stt in zip(pre["scratch"], states)]
         d_means3D, d_means2D, d_colors, d_opacity = pre["d_means3D"], pre["d_means2D"], pre["d_colors"], pre["d_opacity"]
         d_scales, d_rot, d_cov, scratch = pre["d_scales"], pre["d_rot"], pre["d_cov"], pre["scratch"]
 
@@ -706,6 +750,18 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             #                      come back as the gradients of the UNACTIVATED parameters (same shapes)
             rawp = GsrRawParams(_ptr(fused[0]), None, None, _ptr(rotations), _ptr(states[0].act[1]), _ptr(scales),
                                 _ptr(d_rot), _ptr(d_opacity), _ptr(d_scales))
+        if grad_depth is not None:
+            _check(lib.gsr_backward_batch_depth(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                                _ptr(None if per_view_col else colors_precomp),
+                                                _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),
+                                                _ptr_array([stt.binning for stt in states]), _ptr_array([stt.image for stt in states]),
+                                                _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
+                                                _ptr(d_means3D), per_view(d_means2D),
+                                                _ptr(None if (per_view_col or not want_color_grad) else d_colors),
+                                                per_view(d_colors) if (per_view_col and want_color_grad) else None,
+                                                _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), _ptr_array(gd), _stream(dev)),
+                   "gsr_backward_batch_depth")
+            return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
         _check(lib.gsr_backward_batch_raw(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
                                           _ptr(None if per_view_col else colors_precomp),
                                           _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),

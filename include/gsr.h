@@ -63,6 +63,9 @@ size_t gsr_geom_bytes(int32_t P);
 size_t gsr_image_bytes(int32_t image_height, int32_t image_width);
 size_t gsr_binning_bytes(uint32_t num_rendered, int32_t image_height, int32_t image_width);
 size_t gsr_backward_scratch_bytes(int32_t P, uint32_t num_rendered);
+/* scratch of gsr_backward_depth / gsr_backward_batch_depth: gsr_backward_scratch_bytes(P, num_rendered) for the records, then one
+ * float of dL/dz per list entry */
+size_t gsr_backward_scratch_bytes_depth(int32_t P, uint32_t num_rendered);
 
 /* ---- forward, stage 1  (replaces the first half of `rasterize_gaussians`: preprocess + offsets scan)
  * Per Gaussian: frustum cull, projection, 3D->2D covariance, conic, radius, tile rect, colour
@@ -142,14 +145,25 @@ int64_t gsr_wait_block_counts(const volatile uint32_t* words, int32_t nblk, int6
  * dL_dcolors == NULL with colors_precomp means "no colour gradient wanted" (rgb_colors is frozen throughout the reference's
  * training, /root/reference/src/tracking/train_utils.py:133,155): the blend backward then keeps six sums per list entry instead
  * of nine.  Every other gradient is the same up to the rounding of a different reduction tree.
- * Incoming gradients for radii and depth do not exist in this ABI: they are ignored by contract
- * (no reference call site differentiates them, /root/reference/src/tracking/train_utils.py:178,192). */
+ * gsr_backward takes no incoming gradient for radii or depth: they are ignored by contract (no reference call site differentiates
+ * them, /root/reference/src/tracking/train_utils.py:178,192).  The depth gradient is gsr_backward_depth's (below). */
 int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                  const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
                  const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
                  const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                  float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream);
+/* gsr_backward with an incoming gradient for the depth image: dL_ddepth [1,H,W] (device).  The depth D = sum_i alpha_i T_i z_i (z_i:
+ * Gaussian i's view-space depth, no background term) is differentiated as a fourth colour channel whose colour is z_i and whose
+ * background is 0, plus the chain z_i -> means3D, dz/dmeans3D = (view[2], view[6], view[10]) of the column-major viewmatrix.  The
+ * depth term changes dL/dalpha, so it reaches every gradient, not only dL_dmeans3D.  `scratch` must hold
+ * gsr_backward_scratch_bytes_depth(P, num_rendered) bytes.  dL_ddepth == NULL: exactly gsr_backward (same kernels, same result). */
+int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                       const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                       const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                       const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                       float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream);
 
 /* ---- multi-view batch (new design, no counterpart in the reference: its training loop renders one view per
  * optimiser step, /root/reference/src/tracking/train_gs.py:25-39).  The V views of a sharded step share the
@@ -271,6 +285,18 @@ int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32
                        const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
                        float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* stream);
+/* gsr_backward_batch with depth gradients (see gsr_backward_depth): dL_ddepth_views[V] device pointers to [1,H,W], a NULL entry = no
+ * depth gradient for that view.  With any entry set, every view's scratch must hold gsr_backward_scratch_bytes_depth(P, num_rendered[v])
+ * bytes, and views the forward fused into pairs are differentiated unfused (the depth build has no pair pass).  dL_ddepth_views == NULL
+ * or all entries NULL: exactly gsr_backward_batch. */
+int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                             const float* scales, const float* rotations, const float* colors_precomp,
+                             const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                             void* const* binning_states, void* const* image_states, void* batch_state,
+                             const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                             float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                             void* stream);
 
 /* ---- neighbour terms of the t > 0 tracking loss, fused (caller side of the path):
  *   rigid, rot, iso of /root/reference/src/tracking/train_utils.py:198-222 as three means over (foreground point, neighbour).
