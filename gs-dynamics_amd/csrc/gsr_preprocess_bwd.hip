@@ -185,16 +185,25 @@ __device__ __forceinline__ void view_chain(const float* __restrict__ view, const
                                            float tanfovx, float tanfovy, float3 p, const real c[6],
                                            const PartialSum& ps, float gcov[6], float gm3[3], float gm2[2],
                                            float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr, float gz = 0.f) {
-  const real pvx = (real)view[0] * p.x + view[4] * p.y + view[8] * p.z + view[12];
-  const real pvy = (real)view[1] * p.x + view[5] * p.y + view[9] * p.z + view[13];
-  const real pvz = (real)view[2] * p.x + view[6] * p.y + view[10] * p.z + view[14];
+  // The frustum clamp is the forward's decision: the fp32 view-space position, txtz / tytz and limit, with the forward's operations in its
+  // order (both files build with contraction off, so these are its bits).  An fp64 txtz within ~1e-7 of the limit can fall on the other
+  // side, and then dtx / dty would be dropped or added in full.  A clamped coordinate sits at the forward's fp32 limit, widened.
+  const float pvx32 = view[0] * p.x + view[4] * p.y + view[8] * p.z + view[12];
+  const float pvy32 = view[1] * p.x + view[5] * p.y + view[9] * p.z + view[13];
+  const float pvz32 = view[2] * p.x + view[6] * p.y + view[10] * p.z + view[14];
+  const float txtz32 = pvx32 / pvz32, tytz32 = pvy32 / pvz32;
+  const float limx32 = 1.3f * tanfovx, limy32 = 1.3f * tanfovy;
+  const bool xlo = txtz32 < -limx32, xhi = txtz32 > limx32, ylo = tytz32 < -limy32, yhi = tytz32 > limy32;
+  // the rest of the chain in fp64: every operand widened
+  const real pvx = (real)view[0] * (real)p.x + (real)view[4] * (real)p.y + (real)view[8] * (real)p.z + (real)view[12];
+  const real pvy = (real)view[1] * (real)p.x + (real)view[5] * (real)p.y + (real)view[9] * (real)p.z + (real)view[13];
+  const real pvz = (real)view[2] * (real)p.x + (real)view[6] * (real)p.y + (real)view[10] * (real)p.z + (real)view[14];
   const real fx = (real)W / (2.0f * (real)tanfovx), fy = (real)H / (2.0f * (real)tanfovy);
-  const real limx = 1.3f * (real)tanfovx, limy = 1.3f * (real)tanfovy;
   const real tz = pvz;
   const real txtz = pvx / tz, tytz = pvy / tz;
-  const real xm = (txtz < -limx || txtz > limx) ? 0.f : 1.f;
-  const real ym = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
-  const real tx = (txtz < -limx ? -limx : (txtz > limx ? limx : txtz)) * tz, ty = (tytz < -limy ? -limy : (tytz > limy ? limy : tytz)) * tz;
+  const real xm = (xlo || xhi) ? 0.f : 1.f;
+  const real ym = (ylo || yhi) ? 0.f : 1.f;
+  const real tx = (xlo ? -(real)limx32 : (xhi ? (real)limx32 : txtz)) * tz, ty = (ylo ? -(real)limy32 : (yhi ? (real)limy32 : tytz)) * tz;
   const real J00 = fx / tz, J02 = -(fx * tx) / (tz * tz), J11 = fy / tz, J12 = -(fy * ty) / (tz * tz);
   const real T0[3] = {J00 * view[0] + J02 * view[2], J00 * view[4] + J02 * view[6], J00 * view[8] + J02 * view[10]};
   const real T1[3] = {J11 * view[1] + J12 * view[2], J11 * view[5] + J12 * view[6], J11 * view[9] + J12 * view[10]};
@@ -247,9 +256,9 @@ __device__ __forceinline__ void view_chain(const float* __restrict__ view, const
     gm2_first[0] = (float)(-(cA * sx_first + cB * sy_first) * 0.5f * (real)W);
     gm2_first[1] = (float)(-(cC * sy_first + cB * sx_first) * 0.5f * (real)H);
   }
-  const real hx = (real)proj[0] * p.x + proj[4] * p.y + proj[8] * p.z + proj[12];
-  const real hy = (real)proj[1] * p.x + proj[5] * p.y + proj[9] * p.z + proj[13];
-  const real hw = (real)proj[3] * p.x + proj[7] * p.y + proj[11] * p.z + proj[15];
+  const real hx = (real)proj[0] * (real)p.x + (real)proj[4] * (real)p.y + (real)proj[8] * (real)p.z + (real)proj[12];
+  const real hy = (real)proj[1] * (real)p.x + (real)proj[5] * (real)p.y + (real)proj[9] * (real)p.z + (real)proj[13];
+  const real hw = (real)proj[3] * (real)p.x + (real)proj[7] * (real)p.y + (real)proj[11] * (real)p.z + (real)proj[15];
   const real mw = 1.0f / (hw + 0.0000001f);
   const real mul1 = hx * mw * mw, mul2 = hy * mw * mw;
   gm3[0] += (float)(view[0] * dtx + view[1] * dty + view[2] * dtz + (proj[0] * mw - proj[3] * mul1) * m2x + (proj[1] * mw - proj[3] * mul2) * m2y);

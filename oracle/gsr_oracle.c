@@ -62,6 +62,10 @@ static const gsro_f32 *g_over_depth32 = 0;
 void gsro_set_overrides(const int32_t *radii, const int32_t *rect, const gsro_f32 *depth32) {
   g_over_radii = radii; g_over_rect = rect; g_over_depth32 = depth32;
 }
+/* optional frustum-clamp decisions of another (fp32) run: [P,2] uint8 (x, y), 1 = clamped (NULL: computed here).  Near the 1.3 tanfov
+   limit an fp64 txtz can fall on the other side from the fp32 one; with these the forward and the backward take the other run's side. */
+static const uint8_t *g_over_frustum = 0;
+void gsro_set_frustum_override(const uint8_t *frustum_clamped) { g_over_frustum = frustum_clamped; }
 
 #define TILE 16
 #define NEAR_Z 0.2f
@@ -94,6 +98,8 @@ typedef struct {
   float *conic_opacity;  /* [P,4] A,B,C,opacity */
   float *rgb;            /* [P,3] colour fed to the blend */
   uint8_t *clamped;      /* [P,3] SH clamp flags */
+  uint8_t *frustum_clamped; /* [P,2] the 1.3 tanfov clamp of txtz, tytz (A.1-4) was active; 0 for near-culled Gaussians */
+  int frustum_taken;     /* frustum_clamped came from another run (gsro_set_frustum_override): the backward uses it */
   float *cov3D;          /* [P,6] */
   int32_t *radii;        /* [P] */
   int32_t *rect;         /* [P,4] minx,miny,maxx,maxy in tiles */
@@ -185,9 +191,10 @@ static void cov3d_from_scale_rot(const float s_in[3], float mod, const float q[4
 }
 
 /* The 2x3 matrix T = J * W_rot of the EWA projection, with the frustum clamp of A.1-4.
- * Returns clamped tx,ty and the clamp-active flags (used by backward, convention A-3). */
+ * Returns clamped tx,ty and the clamp-active flags (used by backward, convention A-3).  `taken` (NULL: decided here): the flags of
+ * another run; a clamped coordinate goes to the limit on the side of its own txtz / tytz. */
 typedef struct { float T[2][3]; float tx, ty, tz; int xclamped, yclamped; float fx, fy; } ewa_t;
-static void ewa_setup(const gsro_camera *cam, const float pv[3], ewa_t *e) {
+static void ewa_setup(const gsro_camera *cam, const float pv[3], ewa_t *e, const uint8_t *taken) {
   float fx = (float)cam->W / (2.0f * cam->tanfovx);
   float fy = (float)cam->H / (2.0f * cam->tanfovy);
   float limx = 1.3f * cam->tanfovx, limy = 1.3f * cam->tanfovy;
@@ -197,6 +204,11 @@ static void ewa_setup(const gsro_camera *cam, const float pv[3], ewa_t *e) {
   e->yclamped = (tytz < -limy) || (tytz > limy);
   float tx = clampf(txtz, -limx, limx) * tz;
   float ty = clampf(tytz, -limy, limy) * tz;
+  if (taken) {
+    e->xclamped = taken[0] != 0; e->yclamped = taken[1] != 0;
+    tx = (e->xclamped ? (txtz < 0.0f ? -limx : limx) : txtz) * tz;
+    ty = (e->yclamped ? (tytz < 0.0f ? -limy : limy) : tytz) * tz;
+  }
   float J00 = fx / tz, J02 = -(fx * tx) / (tz * tz);
   float J11 = fy / tz, J12 = -(fy * ty) / (tz * tz);
   const float *V = cam->view; /* W_rot(r,c) = V[c*4+r] */
@@ -232,7 +244,8 @@ static void preprocess_one(gsro_ctx *c, int i) {
   memcpy(c->cov3D + 6 * i, cov6, sizeof cov6);
 
   ewa_t e;
-  ewa_setup(cam, pv, &e);
+  ewa_setup(cam, pv, &e, g_over_frustum ? g_over_frustum + 2 * i : 0);
+  c->frustum_clamped[2 * i] = (uint8_t)e.xclamped; c->frustum_clamped[2 * i + 1] = (uint8_t)e.yclamped;
   /* cov2D = T Sigma T^T (A.1-4) */
   float S[3][3] = {{cov6[0], cov6[1], cov6[2]}, {cov6[1], cov6[3], cov6[4]}, {cov6[2], cov6[4], cov6[5]}};
   float U[2][3]; /* U = T Sigma */
@@ -351,7 +364,7 @@ static void render_tile_fwd(gsro_ctx *c, int tile) {
 
 void gsro_free(gsro_ctx *c) {
   if (!c) return;
-  free(c->means2D); free(c->depth); free(c->conic_opacity); free(c->rgb); free(c->clamped);
+  free(c->means2D); free(c->depth); free(c->conic_opacity); free(c->rgb); free(c->clamped); free(c->frustum_clamped);
   free(c->cov3D); free(c->radii); free(c->rect); free(c->tiles_touched); free(c->offsets);
   free(c->keys); free(c->point_list); free(c->ranges); free(c->final_T); free(c->n_contrib);
   free(c->ambiguous); free(c->out_color); free(c->out_depth);
@@ -371,7 +384,9 @@ gsro_ctx *gsro_forward(const gsro_camera *cam, int P, const float *means3D, cons
   size_t Pn = P > 0 ? (size_t)P : 1, N = (size_t)cam->H * cam->W;
   c->means2D = (float *)calloc(2 * Pn, sizeof(float)); c->depth = (float *)calloc(Pn, sizeof(float));
   c->conic_opacity = (float *)calloc(4 * Pn, sizeof(float)); c->rgb = (float *)calloc(3 * Pn, sizeof(float));
-  c->clamped = (uint8_t *)calloc(3 * Pn, 1); c->cov3D = (float *)calloc(6 * Pn, sizeof(float));
+  c->clamped = (uint8_t *)calloc(3 * Pn, 1); c->frustum_clamped = (uint8_t *)calloc(2 * Pn, 1);
+  c->frustum_taken = g_over_frustum != 0;
+  c->cov3D = (float *)calloc(6 * Pn, sizeof(float));
   c->radii = (int32_t *)calloc(Pn, 4); c->rect = (int32_t *)calloc(4 * Pn, 4);
   c->tiles_touched = (uint32_t *)calloc(Pn, 4); c->offsets = (uint32_t *)calloc(Pn + 1, 4);
   c->ranges = (uint32_t *)calloc(2 * (size_t)c->T, 4);
@@ -605,7 +620,7 @@ void gsro_backward(const gsro_ctx *c, const float *dL_dcolor, float *dL_dmeans3D
     pv[1] = V[1] * p[0] + V[5] * p[1] + V[9] * p[2] + V[13];
     pv[2] = V[2] * p[0] + V[6] * p[1] + V[10] * p[2] + V[14];
     ewa_t e;
-    ewa_setup(cam, pv, &e);
+    ewa_setup(cam, pv, &e, c->frustum_taken ? c->frustum_clamped + 2 * i : 0);
     const float *cv = c->cov3D + 6 * i;
     float S[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
     float U0[3], U1[3]; /* Sigma T0, Sigma T1 */
@@ -711,6 +726,7 @@ const uint32_t *gsro_ranges(const gsro_ctx *c) { return c->ranges; }
 const float *gsro_final_T(const gsro_ctx *c) { return c->final_T; }
 const uint32_t *gsro_n_contrib(const gsro_ctx *c) { return c->n_contrib; }
 const uint8_t *gsro_ambiguous(const gsro_ctx *c) { return c->ambiguous; }
+const uint8_t *gsro_frustum_clamped(const gsro_ctx *c) { return c->frustum_clamped; }
 
 /* A.1-1 only: boolean visibility (mark_visible) */
 void gsro_mark_visible(const float *view, int P, const float *means3D, uint8_t *present) {

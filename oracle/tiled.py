@@ -64,13 +64,15 @@ def _load(f64: bool = False):
         lib.gsro_num_tiles.argtypes = [C.c_void_p]
         for name in ("out_color", "out_depth", "radii", "means2D", "depths", "conic_opacity", "cov3D", "rgb",
                      "rect", "tiles_touched", "offsets", "keys", "point_list", "ranges", "final_T",
-                     "n_contrib", "ambiguous"):
+                     "n_contrib", "ambiguous", "frustum_clamped"):
             fn = getattr(lib, "gsro_" + name)
             fn.restype = C.c_void_p
             fn.argtypes = [C.c_void_p]
         lib.gsro_mark_visible.argtypes = [fp, C.c_int, fp, C.POINTER(C.c_uint8)]
         lib.gsro_set_overrides.restype = None
         lib.gsro_set_overrides.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gsro_set_frustum_override.restype = None
+        lib.gsro_set_frustum_override.argtypes = [C.c_void_p]
         _libs[f64] = lib
     if not f64:
         _lib = _libs[False]
@@ -110,8 +112,8 @@ class TiledOracle:
     def __init__(self, cam: OracleCamera, means3D, opacities, colors_precomp=None, scales=None,
                  rotations=None, shs=None, cov3D_precomp=None, nthreads: int = 1, f64: bool = False, decisions_of=None):
         """``f64``: the fp64 build of the same C file (the inputs are the fp32 values, widened).  ``decisions_of``: a finished fp32
-        ``TiledOracle`` of the same inputs whose discrete decisions (radii, tile rects, binary32 depth sort keys) this run takes over,
-        so that both blend the same tile lists (fp64 runs only)."""
+        ``TiledOracle`` of the same inputs whose discrete decisions (radii, tile rects, binary32 depth sort keys, frustum-clamp flags)
+        this run takes over, so that both blend the same tile lists and differentiate the same function (fp64 runs only)."""
         lib = _load(f64)
         self._lib = lib
         self._real = np.float64 if f64 else np.float32
@@ -141,13 +143,16 @@ class TiledOracle:
         keep = None
         if decisions_of is not None:
             assert f64 and decisions_of._real == np.float32
-            keep = (np.ascontiguousarray(decisions_of.radii), np.ascontiguousarray(decisions_of.rect), np.ascontiguousarray(decisions_of.depths))
+            keep = (np.ascontiguousarray(decisions_of.radii), np.ascontiguousarray(decisions_of.rect), np.ascontiguousarray(decisions_of.depths),
+                    np.ascontiguousarray(decisions_of.frustum_clamped))
             lib.gsro_set_overrides(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data)
+            lib.gsro_set_frustum_override(keep[3].ctypes.data)
         try:
             self._ctx = self._forward(lib, c, i, nthreads)
         finally:
             if keep is not None:
                 lib.gsro_set_overrides(None, None, None)
+                lib.gsro_set_frustum_override(None)
         self.H, self.W = c.H, c.W
         self.num_rendered = int(lib.gsro_num_rendered(self._ctx))
         self.num_tiles = int(lib.gsro_num_tiles(self._ctx))
@@ -208,6 +213,10 @@ class TiledOracle:
     def n_contrib(self): return self._get("n_contrib", np.uint32, (self.H, self.W))
     @property
     def ambiguous(self): return self._get("ambiguous", np.uint8, (self.H, self.W)).astype(bool)
+    @property
+    def frustum_clamped(self):
+        """[P,2] uint8: the 1.3 tanfov clamp of (txtz, tytz) was active (not the SH ``clamped`` flags)."""
+        return self._get("frustum_clamped", np.uint8, (self.P, 2))
 
     def backward(self, dL_dcolor, nthreads: Optional[int] = None):
         """Returns dict of gradients (numpy fp32)."""

@@ -313,3 +313,78 @@ def test_fp64_build_of_o2_pins_the_explicit_backward_and_measures_fp32_condition
     g32, g64 = o32.backward(dL), o64.backward(dL)
     worst = max(row_err(g32[k], g64[k])[0] for k in ("means3D", "scales", "rotations", "opacities", "colors_precomp", "means2D"))
     assert 2e-5 < worst < 5e-4, worst
+
+
+# ---- the frustum clamp decision (A.1-4) at its edge: recorded, and taken over by the fp64 referee
+
+def _clamp_edge_oracles(f64_decisions=True):
+    from util import clamp_edge_camera, clamp_edge_scene
+    cam = clamp_edge_camera()
+    g, edge = clamp_edge_scene(cam, seed=0)
+    kw = dict(colors_precomp=g["colors_precomp"], scales=g["scales"], rotations=g["rotations"], nthreads=4)
+    o32 = TiledOracle(cam, g["means3D"], g["opacities"], **kw)
+    o64 = TiledOracle(cam, g["means3D"], g["opacities"], f64=True, decisions_of=o32 if f64_decisions else None, **kw)
+    return cam, g, edge, o32, o64
+
+
+def test_clamp_edge_scene_is_adversarial():
+    """The scene builder's promise, on the host: every edge Gaussian's fp32 txtz / tytz is within 8 ulp of the limit, at least 16 of
+    them are decided differently by the forward's fp32 arithmetic and the old backward's mixed one (both axes, both signs, both sides),
+    and the fp32 oracle's recorded flags are the forward replica's."""
+    from util import clamp_edge_camera, clamp_edge_scene, frustum_decisions_fp32, frustum_decisions_mixed
+    cam = clamp_edge_camera()
+    g, edge = clamp_edge_scene(cam, seed=0)
+    c32, t32, lim = frustum_decisions_fp32(cam, g["means3D"])
+    cmix = frustum_decisions_mixed(cam, g["means3D"])
+    dist = np.abs(np.abs(t32[edge]) - lim[None]) / np.spacing(lim)[None]
+    assert (dist.min(1) <= 8).all()
+    differ = c32 != cmix
+    assert differ[edge].any(1).sum() >= 16, differ[edge].any(1).sum()
+    for ax in (0, 1):
+        for sgn in (1, -1):
+            rows = edge[differ[edge, ax] & (np.sign(t32[edge, ax]) == sgn)]
+            assert len(rows) > 0, (ax, sgn)
+        assert c32[edge][differ[edge, ax], ax].any() and not c32[edge][differ[edge, ax], ax].all(), ax
+    o32 = TiledOracle(cam, g["means3D"], g["opacities"], colors_precomp=g["colors_precomp"], scales=g["scales"], rotations=g["rotations"])
+    vis = o32.radii > 0
+    assert vis[edge].sum() >= 0.9 * len(edge), "edge Gaussians must reach into the image"
+    assert np.array_equal(o32.frustum_clamped.astype(bool)[vis], c32[vis])
+
+
+def test_fp64_oracle_takes_over_the_frustum_clamp():
+    """With decisions_of the fp64 build reports (and uses) the fp32 run's clamp flags; without, it decides at least one edge Gaussian
+    differently -- so without the take-over a comparison at the edge would be against another function."""
+    _, _, edge, o32, o64 = _clamp_edge_oracles()
+    assert np.array_equal(o64.frustum_clamped, o32.frustum_clamped)
+    _, _, _, _, o64_own = _clamp_edge_oracles(f64_decisions=False)
+    assert (o64_own.frustum_clamped[edge] != o32.frustum_clamped[edge]).any()
+
+
+def test_fp64_referee_with_taken_clamp_is_close_to_fp32_on_edge_rows():
+    """Taking over the flags makes the two builds differentiate the same function: on the edge rows the fp32 oracle's means3D gradient is
+    within fp32 conditioning of the fp64 one (without the take-over, rows whose decision flips are off by O(1))."""
+    cam, g, edge, o32, o64 = _clamp_edge_oracles()
+    dL = np.random.default_rng(5).uniform(-1, 1, (3, cam.image_height, cam.image_width)).astype(np.float32)
+    dL[:, o32.ambiguous] = 0.0
+    g32, g64 = o32.backward(dL), o64.backward(dL)
+    assert row_err(g32["means3D"][edge], g64["means3D"][edge])[0] < 1e-3
+
+
+def test_oracle_outputs_unchanged_without_decisions(golden_dir):
+    """Without decisions_of both builds compute exactly what they did before the clamp flags were recorded (golden generated by the
+    earlier oracle: tests/golden/gen_clamp_edge_goldens.py): radii, fp32 colour and depth, and every gradient, bit for bit."""
+    from util import clamp_edge_camera
+    GRADS = ("means3D", "means2D", "colors_precomp", "opacities", "scales", "rotations")
+    dL = np.random.default_rng(5).uniform(-1, 1, (3, 80, 96)).astype(np.float32)     # as gen_clamp_edge_goldens.loss_image
+    z = np.load(os.path.join(golden_dir, "clamp_edge_oracle.npz"))
+    cam = clamp_edge_camera()
+    g = {k: z[f"in_{k}"] for k in ("means3D", "scales", "rotations", "opacities", "colors_precomp")}
+    for tag, f64 in (("f32", False), ("f64", True)):
+        o = TiledOracle(cam, g["means3D"], g["opacities"], colors_precomp=g["colors_precomp"], scales=g["scales"],
+                        rotations=g["rotations"], nthreads=4, f64=f64)
+        assert np.array_equal(o.radii, z[f"{tag}/radii"]), tag
+        if not f64:
+            assert np.array_equal(o.color, z[f"{tag}/color"]) and np.array_equal(o.depth, z[f"{tag}/depth"])
+        gr = o.backward(dL)
+        for k in GRADS:
+            assert np.array_equal(gr[k], z[f"{tag}/grad_{k}"]), (tag, k)
