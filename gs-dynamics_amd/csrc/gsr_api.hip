@@ -125,7 +125,7 @@ void fill_render_view(GsrRenderView& o, const GsrCam& cam, const GeomState& g, c
                       float* out_color, float* out_depth, const float* dL_dcolor, float4* partials) {
   o.point_list = bs.point_list; o.rec = g.rec; o.bg = cam.bg; o.final_T = im.final_T; o.n_contrib = im.n_contrib;
   o.out_color = out_color; o.out_depth = out_depth; o.dL_dcolor = dL_dcolor; o.rect = g.rect; o.offsets = g.offsets;
-  o.partials = partials; o.ranges = im.ranges; o.partner = -1; o.fused_alias = 0; o.colors = nullptr; o.contrib = bs.contrib;
+  o.partials = partials; o.ranges = im.ranges; o.dL_dalpha = nullptr; o.partner = -1; o.fused_alias = 0; o.colors = nullptr; o.contrib = bs.contrib;
   o.used = g.used; o.tracked = g.counters + 1;
   o.cut_in = nullptr; o.cut_out = nullptr; o.redo = nullptr; o.cut_margin = 1.0f;
 }
@@ -498,14 +498,15 @@ int gsr_forward_render_shared_ex(const gsr_settings* s, int32_t P, uint32_t num_
 }
 
 }  // extern "C"
-// gsr_backward and gsr_backward_depth: dL_ddepth == nullptr is exactly gsr_backward
+// gsr_backward, gsr_backward_depth and gsr_backward_ext: dL_ddepth == dL_dalpha == nullptr is exactly gsr_backward
 static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                         const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
                         const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
                         const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream) {
-  GsrRange _range(dL_ddepth ? "gsr_backward_depth" : "gsr_backward");
+                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
+                        const float* dL_dalpha, void* stream) {
+  GsrRange _range(dL_ddepth ? "gsr_backward_depth" : (dL_dalpha ? "gsr_backward_alpha" : "gsr_backward"));
   GsrCam cam;
   if (int rc = make_cam(s, &cam)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -528,6 +529,7 @@ static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered,
     rt.no_colour_grad = (!shs && !dL_dcolors) ? 1 : 0;   // precomputed colours and no gradient wanted for them
     rt.avg_list = num_rendered / (uint32_t)(cam.T > 0 ? cam.T : 1);
     fill_render_view(rt.v[0], cam, g, bs, im, nullptr, nullptr, dL_dcolor, partials);
+    rt.v[0].dL_dalpha = dL_dalpha;
     GsrDepthViews dv;
     if (dL_dz) { dv.dL_ddepth[0] = dL_ddepth; dv.dL_dz[0] = dL_dz; }
     if (int rc = gsr_launch_render_bwd(rt, st, dL_dz ? &dv : nullptr)) return rc;
@@ -545,7 +547,7 @@ int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const 
                  float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream) {
   return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
                       image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, nullptr, stream);
+                      dL_dcov3D, dL_dsh, nullptr, nullptr, stream);
 }
 }  // extern "C"
 static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
@@ -555,7 +557,7 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw,
-                          const float* const* dL_ddepth_views, void* stream);
+                          const float* const* dL_ddepth_views, const float* const* dL_dalpha_views, void* stream);
 extern "C" {
 int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
@@ -565,7 +567,34 @@ int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, 
                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream) {
   return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
                       image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, dL_ddepth, stream);
+                      dL_dcov3D, dL_dsh, dL_ddepth, nullptr, stream);
+}
+int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
+                     const float* dL_dalpha, void* stream) {
+  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
+                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                      dL_dcov3D, dL_dsh, dL_ddepth, dL_dalpha, stream);
+}
+
+int gsr_alpha_views(int32_t V, int32_t H, int32_t W, void* const* image_states, float* out_alpha, void* stream) {
+  GsrRange _range("gsr_alpha_views");
+  if (V <= 0 || V > GSR_MAX_BATCH || H <= 0 || W <= 0) { gsr_set_error("gsr_alpha_views: V must be in 1..%d and H, W positive", GSR_MAX_BATCH); return -2; }
+  if (!image_states || !out_alpha) { gsr_set_error("gsr_alpha_views: NULL argument"); return -2; }
+  GsrAlphaViews tab;
+  tab.V = V; tab.N = H * W;
+  for (int v = 0; v < V; ++v) {
+    if (!image_states[v]) { gsr_set_error("gsr_alpha_views: NULL image state"); return -2; }
+    ImageState im;
+    gsr_carve_image(image_states[v], H, W, &im);
+    tab.final_T[v] = im.final_T;
+    tab.out[v] = out_alpha + (size_t)v * H * W;
+  }
+  return gsr_launch_alpha(tab, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------ multi-view batch
@@ -723,7 +752,21 @@ int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const 
                              void* stream) {
   return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
                         binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, stream);
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, nullptr, stream);
+}
+
+int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                           const float* scales, const float* rotations, const float* colors_precomp,
+                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                           void* const* binning_states, void* const* image_states, void* batch_state,
+                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                           const float* const* dL_dalpha_views, void* stream) {
+  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, dL_dalpha_views,
+                        stream);
 }
 
 int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
@@ -736,11 +779,12 @@ int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const ui
                        float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, void* stream) {
   return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
                         binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, raw, nullptr, stream);
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, raw, nullptr, nullptr, stream);
 }
 }  // extern "C"
 
-// gsr_backward_batch_raw and gsr_backward_batch_depth: dL_ddepth_views == nullptr (or all of its entries nullptr) is exactly the former
+// gsr_backward_batch_raw, gsr_backward_batch_depth and gsr_backward_batch_ext: dL_ddepth_views and dL_dalpha_views == nullptr (or all of
+// their entries nullptr) is exactly the first
 static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp,
                        const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
@@ -749,8 +793,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
                        float* const* dL_dmeans2D,
                        float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
                        float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, const float* const* dL_ddepth_views,
-                       void* stream) {
-  GsrRange _range(dL_ddepth_views ? "gsr_backward_batch_depth" : "gsr_backward_batch");
+                       const float* const* dL_dalpha_views, void* stream) {
+  GsrRange _range(dL_ddepth_views ? "gsr_backward_batch_depth" : (dL_dalpha_views ? "gsr_backward_batch_alpha" : "gsr_backward_batch"));
   if (int rc = check_batch("gsr_backward_batch", V, s, batch_state)) return rc;
   if (int rc = check_geometry_of(V, geometry_of)) return rc;
   if (!num_rendered || !radii || !geom_states || !binning_states || !image_states || !dL_dcolor || !scratch ||
@@ -805,6 +849,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
     if (v == 0) { render_header(rt, V, cam, b.order, b.queue); rt.no_colour_grad = (!dL_dcolors && !dL_dcolors_views) ? 1 : 0; }
     fill_render_view(rt.v[v], cam, g, bs, im, nullptr, nullptr, dL_dcolor[v], (float4*)scratch[v]);
     rt.v[v].ranges = im_owner.ranges;
+    // alpha: one more per-pixel term of the blend backward, fused pairs included (each view of a pair brings its own image)
+    rt.v[v].dL_dalpha = dL_dalpha_views ? dL_dalpha_views[v] : nullptr;
     rt.v[v].partner = partner[v]; rt.v[v].fused_alias = fused[v];
     if (v == 0) { bt.V = V; bt.T = cam.T; bt.gx = cam.gx; bt.order = b.order; bt.queue = b.queue; bt.counts_out = nullptr; bt.P = P; bt.wave_cap = 512; bt.rows = 0; bt.forward_only = 0; }
     bt.v[v].ranges = im_owner.ranges; bt.v[v].fused_alias = (uint32_t)fused[v]; bt.v[v].shares_lists = owner != v;

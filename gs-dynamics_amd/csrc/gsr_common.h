@@ -237,6 +237,7 @@ struct GsrRenderView {         // blend forward / backward
   float* final_T; uint32_t* n_contrib; float* out_color; float* out_depth;
   const float* dL_dcolor; const uint2* rect; const uint32_t* offsets; float4* partials;
   const uint2* ranges;
+  const float* dL_dalpha;   // backward: this view's incoming dL/dalpha image [H,W] (alpha = 1 - final_T); nullptr = no alpha gradient
   const float* colors;   // != nullptr (fused alias of a forward-only call): this view's colours [P,3]; it has no records of its own
   uint8_t* contrib;      // the lists' per-entry quad-contribution bytes (BinningState::contrib of the view that owns the lists)
   uint8_t* used; uint32_t* tracked;   // this view's GeomState::used / &counters[1] (forward: written; see GeomState)
@@ -300,6 +301,11 @@ struct GsrDepthViews { const float* dL_ddepth[GSR_MAX_BATCH]; float* dL_dz[GSR_M
 // the scratch of a depth backward: the record array (gsr_backward_scratch_bytes), then the dL/dz array
 static inline size_t gsr_depth_scratch_offset(uint32_t D) { return gsr_align((size_t)(D ? D : 1) * GSR_PARTIAL_FLOATS * 4); }
 int gsr_launch_render_bwd(const GsrRenderViews& tab, hipStream_t st, const GsrDepthViews* depth = nullptr);
+// the blend backward's kernel arguments (the table, and the depth build's GsrDepthViews behind it) must stay within 4 KB
+static_assert(sizeof(GsrRenderViews) + sizeof(GsrDepthViews) <= 4096, "render_bwd kernel arguments above 4 KB");
+// Rendered alpha (gsr_alpha_views): out_alpha[v][pix] = 1 - final_T of view v's image state, every view of a call in one launch
+struct GsrAlphaViews { int V, N; const float* final_T[GSR_MAX_BATCH]; float* out[GSR_MAX_BATCH]; };
+int gsr_launch_alpha(const GsrAlphaViews& tab, hipStream_t st);
 int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, const float* scales,
                               const float* rotations, const float* colors_precomp, const float* shs,
                               const float* cov3D_precomp, const int32_t* radii, const GeomState& g,

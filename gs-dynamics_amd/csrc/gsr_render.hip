@@ -509,7 +509,7 @@ struct BwdLdsT {
   int sQuadLast[4];                            // per wave: the deepest list position any of its 64 pixels used
 };
 
-struct BwdPartner { const float4* rec; const float* bg; const float* dL_dcolor; };
+struct BwdPartner { const float4* rec; const float* bg; const float* dL_dcolor; const float* dL_dalpha; };
 
 // Differentiable depth (DEPTH builds, plain passes only).  The depth image D = sum_i alpha_i T_i z_i is a fourth colour channel with colour
 // z_i and background 0: its incoming gradient dLd adds z * dLd to each entry's colour dot product (so dL/dalpha, and through it every
@@ -540,7 +540,7 @@ __device__ __forceinline__ void bwd_tile(
     const int tile, const uint2 rg, BwdLdsT<PAIR, NBB>& L, int W, int H, int gx,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, const float* __restrict__ bg,
     const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dcolor,
-    float4* __restrict__ partials, const uint8_t* __restrict__ contrib, const uint8_t* __restrict__ used, const BwdPartner pt,
+    const float* __restrict__ dL_dalpha, float4* __restrict__ partials, const uint8_t* __restrict__ contrib, const uint8_t* __restrict__ used, const BwdPartner pt,
     BwdDepthLds<NBB>* LZ = nullptr, const BwdDepth dp = BwdDepth{nullptr, nullptr}) {
   static_assert(!(DEPTH && PAIR), "no fused-pair depth build");
   constexpr int BB = NBB;
@@ -563,7 +563,10 @@ __device__ __forceinline__ void bwd_tile(
   if (inside) { dL0 = dL_dcolor[pix]; dL1 = dL_dcolor[N + pix]; dL2 = dL_dcolor[2 * N + pix]; }
   float dLd = 0.f;   // DEPTH: this pixel's dL/ddepth (depth has no background term: nTfbg is unchanged)
   if (DEPTH && inside && dp.dL_ddepth) dLd = dp.dL_ddepth[pix];
-  const float nTfbg = -T_final * (bg[0] * dL0 + bg[1] * dL1 + bg[2] * dL2);
+  float nTfbg = -T_final * (bg[0] * dL0 + bg[1] * dL1 + bg[2] * dL2);
+  // Rendered alpha A = 1 - T_final: dA/dalpha_i = T_final / (1 - alpha_i), the background term's form -- its gradient dLa only moves
+  // this per-pixel constant, nTfbg += T_final dLa (uniform test: without an alpha gradient the arithmetic is the plain one)
+  if (dL_dalpha && inside) nTfbg = __builtin_fmaf(T_final, dL_dalpha[pix], nTfbg);
   float T = T_final;
   // Colour accumulated behind the current entry, only ever used dotted with this pixel's dL/dcolour: kept as that dot
   // product (acc_dot), with the previous entry's colour . dL (last_cdot) pending -- 6 VALU per entry instead of 12.
@@ -574,6 +577,7 @@ __device__ __forceinline__ void bwd_tile(
   if (PAIR) {
     if (inside) { dL3 = pt.dL_dcolor[pix]; dL4 = pt.dL_dcolor[N + pix]; dL5 = pt.dL_dcolor[2 * N + pix]; }
     nTfbg2 = -T_final * (pt.bg[0] * dL3 + pt.bg[1] * dL4 + pt.bg[2] * dL5);
+    if (pt.dL_dalpha && inside) nTfbg2 = __builtin_fmaf(T_final, pt.dL_dalpha[pix], nTfbg2);   // the partner's own alpha gradient
   }
 
   GSR_T0();
@@ -836,7 +840,7 @@ __device__ __forceinline__ void bwd_tile(
 // the per-Gaussian used flags are trusted by the backward only when the view's `tracked` word says a tracking forward wrote them
 #define GSR_FWD_MARK_TRACKED() if (TRACK) { if (threadIdx.x < (unsigned)tab.V && tab.v[threadIdx.x].tracked) *tab.v[threadIdx.x].tracked = 1u; }
 #define GSR_BWD_PASS(vw) \
-  tab.W, tab.H, tab.gx, (vw).point_list, (vw).rec, (vw).bg, (vw).final_T, (vw).n_contrib, (vw).dL_dcolor, (vw).partials,                 \
+  tab.W, tab.H, tab.gx, (vw).point_list, (vw).rec, (vw).bg, (vw).final_T, (vw).n_contrib, (vw).dL_dcolor, (vw).dL_dalpha, (vw).partials, \
   /* a forward that did not track (GSR_FORWARD_ONLY -- against the contract, but cheap to survive) left neither contribution bytes nor   \
      used flags: every quad then stages every entry below the tile's deepest contributor (the per-pixel hit test keeps the result exact) */ \
   (!(vw).tracked || *(vw).tracked != 0u) ? (vw).contrib : nullptr,                                                                        \
@@ -921,7 +925,7 @@ __global__ __launch_bounds__(GSR_BLOCK, TRACK ? (PAIRS ? 5 : FWD_TRACK_WAVES) : 
   }
 }
 
-__device__ __forceinline__ BwdPartner bwd_partner(const GsrRenderView& p) { return BwdPartner{p.rec, p.bg, p.dL_dcolor}; }
+__device__ __forceinline__ BwdPartner bwd_partner(const GsrRenderView& p) { return BwdPartner{p.rec, p.bg, p.dL_dcolor, p.dL_dalpha}; }
 
 // LDS of a backward workgroup: the pair build also runs plain tickets (views without a partner), whose layout is the larger one
 template <bool PAIRS, int NBB = BWD_BATCH>   // NBB: batch size of the plain tickets
@@ -1333,19 +1337,20 @@ __device__ __forceinline__ void pc_consumer(PcLds& L, const GsrRenderViews& tab,
   float acc_dot = 0.f, last_cdot = 0.f, last_alpha = 0.f;
   int last = 0;
   // the NEXT tile's per-pixel values, requested while the current tile is still replayed (have_next = sequence number of its first batch + 1)
-  float nT = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f;
+  float nT = 0.f, n0 = 0.f, n1 = 0.f, n2 = 0.f, nA = 0.f;   // nA: dL/dalpha (views with an alpha gradient)
   uint32_t nlast = 0u, have_next = 0u;
   const int red6 = lane >= 48 ? gsr_sum6_slot(lane) : -1;
   (void)red6;
-  auto pixel_loads = [&](int sl, float& t_, uint32_t& l_, float& a_, float& b_, float& c_) {
+  auto pixel_loads = [&](int sl, float& t_, uint32_t& l_, float& a_, float& b_, float& c_, float& d_) {
     const int tile = (int)pc_peek(&L.tile[sl]);
     const GsrRenderView& vw = tab.v[pc_peek(&L.view[sl])];
     const int px = (tile % gx) * GSR_TILE + GSR_QW * (wv & 1) + (lane & 7), py = (tile / gx) * GSR_TILE + GSR_QH * (wv >> 1) + (lane >> 3);
-    t_ = 0.f; l_ = 0u; a_ = 0.f; b_ = 0.f; c_ = 0.f;
+    t_ = 0.f; l_ = 0u; a_ = 0.f; b_ = 0.f; c_ = 0.f; d_ = 0.f;
     if (px < W && py < H) {
       const int pix = py * W + px;
       t_ = vw.final_T[pix]; l_ = vw.n_contrib[pix];
       a_ = vw.dL_dcolor[pix]; b_ = vw.dL_dcolor[N + pix]; c_ = vw.dL_dcolor[2 * N + pix];
+      if (vw.dL_dalpha) d_ = vw.dL_dalpha[pix];
     }
   };
   __builtin_amdgcn_s_setprio(PC_CONS_PRIO);  // (its waits drop to 0)
@@ -1359,20 +1364,21 @@ __device__ __forceinline__ void pc_consumer(PcLds& L, const GsrRenderViews& tab,
     if (flags & PC_FLAG_FIRST) {             // a new tile: this quad's pixels
       const int tile = (int)pc_peek(&L.tile[sl]);
       const GsrRenderView& vw = tab.v[pc_peek(&L.view[sl])];
-      if (have_next != seq + 1u) pixel_loads(sl, nT, nlast, n0, n1, n2);
+      if (have_next != seq + 1u) pixel_loads(sl, nT, nlast, n0, n1, n2, nA);
       have_next = 0u;
       pxf = (float)((tile % gx) * GSR_TILE + GSR_QW * (wv & 1) + (lane & 7));
       pyf = (float)((tile / gx) * GSR_TILE + GSR_QH * (wv >> 1) + (lane >> 3));
       const float T_final = nT;
       last = (int)nlast; dL0 = n0; dL1 = n1; dL2 = n2;
       nTfbg = -T_final * (vw.bg[0] * dL0 + vw.bg[1] * dL1 + vw.bg[2] * dL2);
+      if (vw.dL_dalpha) nTfbg = __builtin_fmaf(T_final, nA, nTfbg);   // rendered alpha (see bwd_tile)
       T = T_final;
       acc_dot = 0.f; last_cdot = 0.f; last_alpha = 0.f;
     }
     // the batch behind this one already opens the next tile: ask for its pixels now
     if (have_next == 0u && pc_peek(&L.prod_seq) > seq + 1u) {
       const int sn = (int)((seq + 1u) % PC_R);
-      if (pc_peek(&L.flags[sn]) == PC_FLAG_FIRST) { pixel_loads(sn, nT, nlast, n0, n1, n2); have_next = seq + 2u; }
+      if (pc_peek(&L.flags[sn]) == PC_FLAG_FIRST) { pixel_loads(sn, nT, nlast, n0, n1, n2, nA); have_next = seq + 2u; }
     }
 #ifdef GSR_TILE_TIMING
     if (wv == 0) { if (flags & PC_FLAG_FIRST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PC_TP(1); }
@@ -1492,8 +1498,37 @@ __global__ __launch_bounds__(PC_THREADS, PC_WAVES_PER_EU) __attribute__((amdgpu_
   }
 }
 
+// Rendered alpha (gsr_alpha_views): out[v][pix] = 1 - final_T[v][pix] for the V views of a call, one launch (blockIdx.y = view).  It reads
+// the image state each forward mode leaves behind -- fused partners and empty tiles included -- so the blend kernels stay untouched.
+// Four pixels per thread: float4 when the view's two arrays are 16-byte aligned and N % 4 == 0 (uniform), scalars otherwise.
+#define ALPHA_THREADS 256
+__global__ __launch_bounds__(ALPHA_THREADS) void alpha_views(GsrAlphaViews tab) {
+  const int v = blockIdx.y;
+  const float* __restrict__ T = tab.final_T[v];
+  float* __restrict__ out = tab.out[v];
+  const size_t N = (size_t)tab.N;
+  const bool vec = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  for (size_t i = ((size_t)blockIdx.x * ALPHA_THREADS + threadIdx.x) * 4; i < N; i += (size_t)gridDim.x * ALPHA_THREADS * 4) {
+    if (vec) {
+      const float4 t = *reinterpret_cast<const float4*>(T + i);
+      *reinterpret_cast<float4*>(out + i) = make_float4(1.0f - t.x, 1.0f - t.y, 1.0f - t.z, 1.0f - t.w);
+    } else {
+      for (size_t k = i; k < i + 4 && k < N; ++k) out[k] = 1.0f - T[k];
+    }
+  }
+}
+
 }  // namespace gsr_render
 using namespace gsr_render;
+
+int gsr_launch_alpha(const GsrAlphaViews& tab, hipStream_t st) {
+  if (tab.V <= 0 || tab.N <= 0) return 0;
+  const int per_view = (int)(((size_t)tab.N + 4 * ALPHA_THREADS - 1) / (4 * ALPHA_THREADS));
+  { GSR_PROF("alpha", st);
+    hipLaunchKernelGGL(alpha_views, dim3(per_view < 2048 ? per_view : 2048, tab.V), dim3(ALPHA_THREADS), 0, st, tab); }
+  GSR_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 // Debug: copy out and clear the forward phase timers (zeros in a normal build).
 int gsr_debug_fwd_timing(unsigned long long* out16) {

@@ -270,7 +270,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
-                             const c10::optional<torch::Tensor>& dL_dout_depth) {   // extension (default None): [1, H, W] -> gsr_backward_depth
+                             const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W] -> gsr_backward_depth
+                             const c10::optional<torch::Tensor>& dL_dout_alpha) {  // extension (default None): [1, H, W] -> gsr_backward_ext
   const c10::Device dev = means3D.device();
   c10::hip::HIPGuard guard(dev.index());
   const int64_t P = means3D.size(0);
@@ -302,17 +303,21 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev);
   void* stream = (void*)c10::hip::getCurrentHIPStream(dev.index()).stream();
   auto optr = [](torch::Tensor& t) -> float* { return t.numel() ? t.data_ptr<float>() : nullptr; };
-  if (dL_dout_depth.has_value() && dL_dout_depth->defined()) {   // differentiable depth: the depth build, its larger scratch
-    TORCH_CHECK(dL_dout_depth->numel() == H * W, "dL_dout_depth must hold H * W elements ([1, H, W])");
-    const torch::Tensor gd = f32c(*dL_dout_depth, dev);
-    torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)},
+  const bool has_depth = dL_dout_depth.has_value() && dL_dout_depth->defined();
+  const bool has_alpha = dL_dout_alpha.has_value() && dL_dout_alpha->defined();
+  if (has_depth || has_alpha) {   // differentiable depth (the depth build, its larger scratch) and / or the rendered alpha's gradient
+    TORCH_CHECK(!has_depth || dL_dout_depth->numel() == H * W, "dL_dout_depth must hold H * W elements ([1, H, W])");
+    TORCH_CHECK(!has_alpha || dL_dout_alpha->numel() == H * W, "dL_dout_alpha must hold H * W elements ([1, H, W])");
+    const torch::Tensor gd = has_depth ? f32c(*dL_dout_depth, dev) : torch::Tensor(), ga = has_alpha ? f32c(*dL_dout_alpha, dev) : torch::Tensor();
+    torch::Tensor scratch = torch::empty({(int64_t)(has_depth ? gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)
+                                                               : gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R))},
                                          torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-    check(gsr_backward_depth(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
-                             radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
-                             g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
-                             optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
-                             gd.data_ptr<float>(), stream),
-          "gsr_backward_depth");
+    check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
+                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
+          "gsr_backward_ext");
     return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
   }
   torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R)},
@@ -329,7 +334,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
 // torch.autograd.Function whose forward / backward each crossed into this layer once and spent ~0.12 ms per camera in the interpreter
 // (profiles/r04_dropin_host_profile.txt); here the whole call is ONE crossing: GaussianRasterizer.forward -> _C.rasterize -> this node.
 // Inputs in the order of upstream's Python _RasterizeGaussians.apply (means3D, means2D, sh, colors_precomp, opacities, scales,
-// rotations, cov3Ds_precomp) followed by the settings record's fields; outputs (color, radii, depth).  means2D is the gradient holder
+// rotations, cov3Ds_precomp) followed by the settings record's fields; outputs (color, radii, depth), and alpha = 1 - final_T [1, H, W]
+// when return_alpha (one gsr_alpha_views launch behind the forward; differentiable through gsr_backward_ext).  means2D is the gradient holder
 // the reference reads back (`rendervar['means2D'].grad`, /root/reference/src/tracking/external.py:139-140): its values are ignored.
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
   static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor means3D, torch::Tensor means2D,
@@ -337,13 +343,24 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                                 torch::Tensor rotations, torch::Tensor cov3D, torch::Tensor bg, torch::Tensor viewmatrix,
                                                 torch::Tensor projmatrix, torch::Tensor campos, double tanfovx, double tanfovy, int64_t H,
                                                 int64_t W, double scale_modifier, int64_t degree, bool prefiltered, bool will_backward,
-                                                bool differentiable_depth) {
+                                                bool differentiable_depth, bool return_alpha) {
     (void)means2D;
-    ctx->set_materialize_grads(false);        // grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it
+    // grad_depth is ignored unless differentiable_depth, an unused alpha has no gradient: do not let autograd fill zero images for them
+    ctx->set_materialize_grads(false);
     ctx->saved_data["depth"] = differentiable_depth;
     Forward r = rasterize_forward(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tanfovx,
                                   tanfovy, H, W, sh, degree, campos, prefiltered, will_backward, true, t_call_state);
     torch::Tensor color = r.color, depth = r.depth, radii = r.radii;
+    torch::Tensor alpha;
+    if (return_alpha) {      // 1 - final_T of this call's own image state (P = 0: nothing blended, alpha 0)
+      alpha = torch::zeros({1, H, W}, color.options());
+      if (means3D.size(0) > 0) {
+        c10::hip::HIPGuard guard(means3D.device().index());
+        void* image_state = r.image.data_ptr();
+        check(gsr_alpha_views(1, (int32_t)H, (int32_t)W, &image_state, alpha.data_ptr<float>(),
+                              (void*)c10::hip::getCurrentHIPStream(means3D.device().index()).stream()), "gsr_alpha_views");
+      }
+    }
     ctx->saved_data["R"] = r.layout;      // what the states were laid out for (the count, or a capacity-mode forward's capacity)
     ctx->saved_data["tanfovx"] = tanfovx; ctx->saved_data["tanfovy"] = tanfovy; ctx->saved_data["scale_modifier"] = scale_modifier;
     ctx->saved_data["degree"] = degree; ctx->saved_data["H"] = H; ctx->saved_data["W"] = W;
@@ -352,10 +369,11 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     ctx->saved_data["empty"] = means3D.size(0) == 0;
     ctx->save_for_backward({means3D, radii, colors, sh, scales, rotations, cov3D, r.geom, r.binning, r.image, bg, viewmatrix, projmatrix, campos});
     ctx->mark_non_differentiable({radii});
+    if (return_alpha) return {color, radii, depth, alpha};
     return {color, radii, depth};
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    torch::autograd::variable_list out(21);       // one slot per forward argument; undefined = no gradient
+    torch::autograd::variable_list out(22);       // one slot per forward argument; undefined = no gradient
     if (ctx->saved_data["empty"].toBool()) return out;
     const auto sv = ctx->get_saved_variables();
     const torch::Tensor &m3 = sv[0], &radii = sv[1], &col = sv[2], &sh = sv[3], &sc = sv[4], &rot = sv[5], &cov = sv[6], &geom = sv[7],
@@ -365,13 +383,16 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     // grads[2] (depth): ignored unless the call opted in (differentiable_depth); then the depth build -- when autograd delivers one
     c10::optional<torch::Tensor> gd;
     if (ctx->saved_data["depth"].toBool() && grads[2].defined()) gd = grads[2];
+    // grads[3] (alpha, when the call returned it): always differentiable -- when autograd delivers one, gsr_backward_ext adds its term
+    c10::optional<torch::Tensor> ga;
+    if (grads.size() > 3 && grads[3].defined()) ga = grads[3];
     if (!g.defined()) g = torch::zeros({3, H, W}, m3.options().dtype(torch::kFloat32));
     const bool has_sh = ctx->saved_data["has_sh"].toBool(), has_col = ctx->saved_data["has_col"].toBool(),
                has_sc = ctx->saved_data["has_sc"].toBool(), has_cov = ctx->saved_data["has_cov"].toBool();
     const bool want_col = has_col && ctx->needs_input_grad(3);      // frozen colours (the reference's training): the six-sum backward
     auto r = rasterize_gaussians_backward(bg, m3, radii, col, sc, rot, ctx->saved_data["scale_modifier"].toDouble(), cov, view, proj,
                                           ctx->saved_data["tanfovx"].toDouble(), ctx->saved_data["tanfovy"].toDouble(), g, sh,
-                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd);
+                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd, ga);
     out[0] = std::get<3>(r);                      // means3D
     out[1] = std::get<0>(r);                      // means2D (x, y in NDC units, z = 0)
     if (has_sh) out[2] = std::get<5>(r);
@@ -386,13 +407,15 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
 // GaussianRasterizer.forward in one call.  Whether a backward can follow is decided HERE, before the node is built: inside a node's
 // forward the grad mode is always off and needs_input_grad reports requires_grad flags even under torch.no_grad() --
 // evaluation renders of trainable parameters under no_grad take the untracked forward (GSR_FORWARD_ONLY).
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+// -> (color, radii, depth), or (color, radii, depth, alpha) with return_alpha
+pybind11::tuple
 rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's state for the device (may be none: nothing remembered)
           const torch::Tensor& means3D, const torch::Tensor& means2D, const torch::Tensor& sh, const torch::Tensor& colors,
           const torch::Tensor& opacities, const torch::Tensor& scales, const torch::Tensor& rotations, const torch::Tensor& cov3D,
           const torch::Tensor& bg, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& campos,
           double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered,
-          bool differentiable_depth) {   // extension: the depth output is differentiated too (gsr_backward_depth)
+          bool differentiable_depth,     // extension: the depth output is differentiated too (gsr_backward_depth)
+          bool return_alpha) {           // extension: a fourth output, the rendered alpha 1 - final_T (differentiable)
   bool will_backward = false;
   if (at::GradMode::is_enabled())
     for (const torch::Tensor* t : {&means3D, &means2D, &sh, &colors, &opacities, &scales, &rotations, &cov3D})
@@ -403,8 +426,9 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
     ~Scope() { t_call_state = prev; }
   } scope(state.get());
   auto o = RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos, tanfovx,
-                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth);
-  return std::make_tuple(o[0], o[1], o[2]);
+                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth, return_alpha);
+  if (return_alpha) return pybind11::make_tuple(o[0], o[1], o[2], o[3]);
+  return pybind11::make_tuple(o[0], o[1], o[2]);
 }
 
 // upstream: markVisible(means3D, viewmatrix, projmatrix) -> bool[P]
@@ -451,12 +475,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"),
         py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"),
         py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"),
-        py::arg("want_color_grad") = true, py::arg("dL_dout_depth") = py::none());
+        py::arg("want_color_grad") = true, py::arg("dL_dout_depth") = py::none(), py::arg("dL_dout_alpha") = py::none());
   // one GaussianRasterizer call: forward + the autograd node (C++); first argument: the LayerState or None
   m.def("rasterize", &rasterize, py::arg("state"), py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"), py::arg("opacities"),
         py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"),
         py::arg("tanfovx"), py::arg("tanfovy"), py::arg("H"), py::arg("W"), py::arg("scale_modifier"), py::arg("degree"), py::arg("prefiltered"),
-        py::arg("differentiable_depth") = false);
+        py::arg("differentiable_depth") = false, py::arg("return_alpha") = false);
   m.def("mark_visible", &mark_visible);
   m.def("abi_version", []() { return (int)GSR_VERSION; });   // the header this layer was COMPILED against (compare with the library's gsr_version())
 }

@@ -95,14 +95,15 @@ def _prep(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 
 
 class _RasterizeGaussians(torch.autograd.Function):
-    """forward -> (color, radii, depth); backward -> grads for the 8 tensor inputs, None for settings."""
+    """forward -> (color, radii, depth[, alpha]); backward -> grads for the 8 tensor inputs, None for settings."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, differentiable_depth=False):
-        # grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it (or for an unused colour)
+                raster_settings, differentiable_depth=False, return_alpha=False):
+        # grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it (or for an unused colour / alpha)
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
+        ctx.alpha = bool(return_alpha)
         m3 = _prep(means3D)
         if m3 is None:
             if means3D is not None and means3D.dim() == 2 and means3D.shape[1] == 3:
@@ -111,7 +112,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 H, W = int(raster_settings.image_height), int(raster_settings.image_width)
                 ctx.empty = True
                 return (torch.zeros((3, H, W), device=dev), torch.zeros((0,), dtype=torch.int32, device=dev),
-                        torch.zeros((1, H, W), device=dev))
+                        torch.zeros((1, H, W), device=dev)) + ((torch.zeros((1, H, W), device=dev),) if ctx.alpha else ())
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         if m3.dim() != 2 or m3.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -130,6 +131,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.has = (sh_.numel() > 0, col_.numel() > 0, sc_.numel() > 0, cov_.numel() > 0)
             ctx.save_for_backward(m3, radii, col_, sh_, sc_, rot_, cov_, geom, binning, image)
             ctx.mark_non_differentiable(radii)
+            if ctx.alpha:     # 1 - final_T of this call's image state (the C++ layer's buffers have the library's layout)
+                st_ = _hip.RasterState()
+                st_.image, st_.H, st_.W, st_.P = image, int(rs.image_height), int(rs.image_width), int(m3.shape[0])
+                return color, radii, depth, _hip.rendered_alpha([st_])[0]
             return color, radii, depth
         ctx.native = None
         sh_, col_, op_ = _prep(sh), _prep(colors_precomp), _prep(opacities)
@@ -142,12 +147,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                               sc_ if sc_ is not None else empty, rot_ if rot_ is not None else empty,
                               cov_ if cov_ is not None else empty)
         ctx.mark_non_differentiable(radii)
+        if ctx.alpha:
+            return color, radii, depth, _hip.rendered_alpha([state])[0]
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth):  # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
+        # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth; grad_alpha: used whenever autograd delivers one
         if ctx.empty:
-            return (None,) * 10
+            return (None,) * 11
         if not ctx.depth:
             grad_depth = None
         if ctx.native is not None:
@@ -160,9 +168,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.bg, m3, radii, col_, sc_, rot_, float(rs.scale_modifier), cov_, rs.viewmatrix, rs.projmatrix, float(rs.tanfovx),
                 float(rs.tanfovy), grad_color, sh_, int(rs.sh_degree), rs.campos, geom, ctx.num_rendered, binning, image,
                 bool(has_col and ctx.needs_input_grad[3]),   # frozen colours (the reference's training): the six-sum backward
-                *(() if grad_depth is None else (grad_depth,)))
+                *(() if grad_depth is None else (grad_depth,)), **({} if grad_alpha is None else {"dL_dout_alpha": grad_alpha}))
             return (d3, d2, dsh if has_sh else None, dc if (has_col and ctx.needs_input_grad[3]) else None, do, ds if has_sc else None, dr if has_sc else None,
-                    dcov if has_cov else None, None, None)
+                    dcov if has_cov else None, None, None, None)
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         if grad_color is None:
@@ -170,22 +178,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh = _hip.rasterize_backward(
             ctx.state, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
-            want_color_grad=bool(has_col and ctx.needs_input_grad[3]), **({} if grad_depth is None else {"grad_depth": grad_depth}))
+            want_color_grad=bool(has_col and ctx.needs_input_grad[3]), **({} if grad_depth is None else {"grad_depth": grad_depth}),
+            **({} if grad_alpha is None else {"grad_alpha": grad_alpha}))
         return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity,
-                d_scales if has_sc else None, d_rot if has_sc else None, d_cov if has_cov else None, None, None)
+                d_scales if has_sc else None, d_rot if has_sc else None, d_cov if has_cov else None, None, None, None)
 
 
 class _RasterizeGaussiansViews(torch.autograd.Function):
     """V views of the same Gaussians in one call (extension of the reference API, which renders one view
-    per call): forward -> (color[V,3,H,W], radii[V,P], depth[V,1,H,W]); backward sums the per-view input
+    per call): forward -> (color[V,3,H,W], radii[V,P], depth[V,1,H,W][, alpha[V,1,H,W]]); backward sums the per-view input
     gradients.  ``means2D`` is a [V,P,3] holder so each view's screen-space gradient stays separate
     (densification accumulates their norms per view, /root/reference/src/tracking/external.py:138-142)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
-                differentiable_depth=False):
+                differentiable_depth=False, return_alpha=False):
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
+        ctx.alpha = bool(return_alpha)
         m3 = _prep(means3D)
         if m3 is None or m3.dim() != 2 or m3.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -202,10 +212,12 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
                               sc_ if sc_ is not None else empty, rot_ if rot_ is not None else empty,
                               cov_ if cov_ is not None else empty)
         ctx.mark_non_differentiable(radii)
+        if ctx.alpha:
+            return color, radii, depth, _hip.rendered_alpha(states)
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth):
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         V = len(ctx.states)
@@ -215,18 +227,22 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
             ctx.states, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
             want_color_grad=bool(has_col and ctx.needs_input_grad[3]),
-            **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}))
+            **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}),
+            **({"grad_alpha": grad_alpha} if grad_alpha is not None else {}))
         # gradients arrive already summed over views (means2D stays per view); the state stays on ctx so that a
         # second backward (retain_graph=True) works, and is released with the graph
         return (d3, d2, dsh if has_sh else None, dc if has_col else None, do, ds if has_sc else None,
-                dr if has_sc else None, dcov if has_cov else None, None, None)
+                dr if has_sc else None, dcov if has_cov else None, None, None, None)
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None, differentiable_depth=False):
+                              rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False):
     """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder.
     ``differentiable_depth``: the depth output [V,1,H,W] is differentiated too (see GaussianRasterizer); views that share a camera,
-    which the backward otherwise fuses into one pass, are then differentiated unfused."""
+    which the backward otherwise fuses into one pass, are then differentiated unfused.
+    ``return_alpha``: a fourth output, the rendered alpha [V,1,H,W] = 1 - final_T, always differentiable (see GaussianRasterizer); views
+    that share a camera stay fused.  A view's ``means2D`` gradient then includes its own alpha term: a caller that wants a colour-only
+    densification statistic must render alpha with a separate call (its own means2D holder)."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -245,16 +261,17 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
             means3D, means2D if whole else means2D[lo:hi], empty if shs is None else shs,
             empty if colors_precomp is None else (colors_precomp[lo:hi] if (per_view_col and not whole) else colors_precomp), opacities,
             empty if scales is None else scales, empty if rotations is None else rotations,
-            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth))
+            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth), bool(return_alpha))
     if V <= _hip.MAX_BATCH:
         return call(0, V)
     # more views than one library call takes: several calls, outputs concatenated (autograd sums the shared inputs)
     parts = [call(lo, min(V, lo + _hip.MAX_BATCH)) for lo in range(0, V, _hip.MAX_BATCH)]
-    return tuple(torch.cat([p[k] for p in parts]) for k in range(3))
+    return tuple(torch.cat([p[k] for p in parts]) for k in range(len(parts[0])))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, differentiable_depth=False):
+                        raster_settings, differentiable_depth=False, return_alpha=False):
+    """One view (upstream's entry point).  ``return_alpha``: a fourth output, the rendered alpha [1,H,W] (see GaussianRasterizer)."""
     native = _native() if (means3D is not None and means3D.is_cuda) else None
     if native is not None and hasattr(native, "rasterize") and not _PY_NODE:
         # one crossing into the torch C++ layer: forward and the autograd node live there (csrc/gsr_torch.cpp: RasterizeFn)
@@ -262,10 +279,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return native.rasterize(layer_state(means3D.device), means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg, rs.viewmatrix,
                                 rs.projmatrix, rs.campos, float(rs.tanfovx), float(rs.tanfovy), int(rs.image_height), int(rs.image_width),
                                 float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered),
-                                *((True,) if differentiable_depth else ()))
-    if differentiable_depth:
+                                *((bool(differentiable_depth), True) if return_alpha else ((True,) if differentiable_depth else ())))
+    if differentiable_depth or return_alpha:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings, True)
+                                         cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings)
 
@@ -276,12 +293,20 @@ class GaussianRasterizer(nn.Module):
 
     ``differentiable_depth`` (extension, default False): the depth output is differentiated too.  D = sum_i alpha_i T_i z_i (z_i: the
     Gaussian's view-space depth, no background term) is treated as a fourth colour channel with colour z_i and background 0, plus
-    z_i -> means3D; the depth term reaches every input gradient through dL/dalpha.  False: the depth gradient is ignored, as upstream."""
+    z_i -> means3D; the depth term reaches every input gradient through dL/dalpha.  False: the depth gradient is ignored, as upstream.
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False):
+    ``return_alpha`` (extension, default False): forward returns a fourth tensor, the rendered alpha [1,H,W] = 1 - final_T (the forward's
+    own transmittance after the last blended entry; 0 where nothing was blended) -- the mask the reference renders a second time with
+    colours = 1 on black.  It is always differentiable: its gradient reaches means2D, opacities, the covariance (scales / rotations or
+    cov3D_precomp) and means3D, never the colours or SHs.  ``means2D.grad`` then includes the alpha term, as autograd requires: a caller
+    that wants a colour-only densification statistic must render alpha with a separate call (its own means2D holder).  False: upstream's
+    three outputs."""
+
+    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False, return_alpha: bool = False):
         super().__init__()
         self.raster_settings = raster_settings
         self.differentiable_depth = bool(differentiable_depth)
+        self.return_alpha = bool(return_alpha)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -304,8 +329,8 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if self.differentiable_depth:
+        if self.differentiable_depth or self.return_alpha:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, rs, differentiable_depth=True)
+                                       cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs)

@@ -71,7 +71,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_batch_state_bytes", "gsr_forward_preprocess_batch", "gsr_forward_render_batch", "gsr_forward_batch",
            "gsr_forward_batch_capacity", "gsr_forward_batch_capacity_raw",
            "gsr_backward_batch", "gsr_backward_batch_raw", "gsr_backward_depth", "gsr_backward_batch_depth",
-           "gsr_backward_scratch_bytes_depth", "gsr_debug_phase_timing",
+           "gsr_backward_scratch_bytes_depth", "gsr_backward_ext", "gsr_backward_batch_ext", "gsr_alpha_views", "gsr_debug_phase_timing",
            "gsr_image_loss_blocks", "gsr_image_loss_forward", "gsr_image_loss_backward", "gsr_fps", "gsr_fps_scratch_bytes", "gsr_fit_rotations", "gsr_fit_bones", "gsr_fps_thin", "gsr_construct_edges", "gsr_lbs_valid", "gsr_lbs",
            "gsr_rigidity_blocks", "gsr_rigidity_forward", "gsr_rigidity_backward",
            "gsr_views_loss_blocks", "gsr_views_loss_forward", "gsr_views_loss_backward", "gsr_target_moments",
@@ -108,6 +108,8 @@ def load_library():
     lib.gsr_backward.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 20 + [vp]
     lib.gsr_backward_depth.restype = C.c_int
     lib.gsr_backward_depth.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 21 + [vp]
+    lib.gsr_backward_ext.restype = C.c_int
+    lib.gsr_backward_ext.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 22 + [vp]
     PS = C.POINTER(GsrSettings)
     PV = C.POINTER(C.c_void_p)
     lib.gsr_batch_state_bytes.restype = sz; lib.gsr_batch_state_bytes.argtypes = [i32, i32, i32, i32]
@@ -130,6 +132,10 @@ def load_library():
     lib.gsr_backward_batch_raw.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [C.POINTER(GsrRawParams), vp]
     lib.gsr_backward_batch_depth.restype = C.c_int
     lib.gsr_backward_batch_depth.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, vp]
+    lib.gsr_backward_batch_ext.restype = C.c_int
+    lib.gsr_backward_batch_ext.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, PV, vp]
+    lib.gsr_alpha_views.restype = C.c_int
+    lib.gsr_alpha_views.argtypes = [i32, i32, i32, PV, vp, vp]
     lib.gsr_image_loss_blocks.restype = i32
     lib.gsr_image_loss_blocks.argtypes = [i32, i32, i32]
     lib.gsr_image_loss_forward.restype = C.c_int
@@ -359,11 +365,11 @@ def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotat
 
 
 def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_precomp, shs, scales, rotations,
-                       cov3D_precomp, want_color_grad: bool = True, grad_depth=None):
+                       cov3D_precomp, want_color_grad: bool = True, grad_depth=None, grad_alpha=None):
     """K7..K9.  Returns (dmeans3D, dmeans2D, dcolors, dopacity[P,1], dscales, drotations, dcov3D, dsh).
     ``want_color_grad=False`` (precomputed colours that need no gradient): dcolors is None and the blend backward keeps six sums
     per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (gsr_backward_depth); None is
-    exactly gsr_backward."""
+    exactly gsr_backward.  ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient (gsr_backward_ext); None adds nothing."""
     lib = load_library()
     dev = means3D.device
     P, D = state.P, state.num_rendered
@@ -379,6 +385,20 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
         d_rot = torch.empty((P, 4), **f32) if cov3D_precomp is None else None
         d_cov = torch.empty((P, 6), **f32)
         d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
+        if grad_alpha is not None:
+            gd = None if grad_depth is None else grad_depth.to(**f32).contiguous()
+            ga = grad_alpha.to(**f32).contiguous()
+            for name, t in (("grad_depth", gd), ("grad_alpha", ga)):
+                if t is not None and t.numel() != state.H * state.W:
+                    raise ValueError(f"rasterize_backward: {name} must hold H * W = {state.H * state.W} elements ([1, H, W]), got {t.numel()}")
+            sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
+            scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
+            _check(lib.gsr_backward_ext(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                        _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
+                                        _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
+                                        _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
+                                        _ptr(d_cov), _ptr(d_sh), _ptr(gd), _ptr(ga), _stream(dev)), "gsr_backward_ext")
+            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
         if grad_depth is not None:
             gd = grad_depth.to(**f32).contiguous()
             if gd.numel() != state.H * state.W:
@@ -692,12 +712,14 @@ def forward_counts_ok(states) -> bool:
 
 
 def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp, shs, scales, rotations, cov3D_precomp,
-                             want_color_grad: bool = True, grad_out=None, grad_depth=None):
+                             want_color_grad: bool = True, grad_out=None, grad_depth=None, grad_alpha=None):
     """Backward of all views.  Returns gradients already SUMMED over views (dmeans3D[P,3], dcolors, dopacity[P,1],
     dscales, drotations, dcov3D, dsh) plus the per-view means2D gradients [V,P,3].
     ``grad_depth`` ([V,1,H,W], or a sequence of V such images or None, or None): the depth images' gradient (gsr_backward_batch_depth:
     views the forward fused into pairs are differentiated unfused; a None entry = no depth gradient for that view); None, or no image
-    at all, is exactly gsr_backward_batch."""
+    at all, is exactly gsr_backward_batch.
+    ``grad_alpha`` (same forms): the rendered alphas' gradient (gsr_backward_batch_ext: fused pairs stay fused; a None entry = no alpha
+    gradient for that view); None, or no image at all, adds nothing."""
     lib = load_library()
     dev = means3D.device
     V = len(states)
@@ -710,9 +732,15 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             raise ValueError(f"rasterize_backward_batch: grad_depth must have one entry per view ({V})")
         if all(d is None for d in grad_depth):
             grad_depth = None
+    if grad_alpha is not None and not isinstance(grad_alpha, torch.Tensor):
+        if len(grad_alpha) != V:
+            raise ValueError(f"rasterize_backward_batch: grad_alpha must have one entry per view ({V})")
+        if all(a is None for a in grad_alpha):
+            grad_alpha = None
     if shs is not None:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
         outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp,
-                                   grad_depth=None if grad_depth is None else grad_depth[v])
+                                   grad_depth=None if grad_depth is None else grad_depth[v],
+                                   grad_alpha=None if grad_alpha is None else grad_alpha[v])
                 for v in range(V)]
         sm = lambda k: None if outs[0][k] is None else torch.stack([o[k] for o in outs]).sum(0)  # noqa: E731
         return sm(0), torch.stack([o[1] for o in outs]), None, sm(3), sm(4), sm(5), sm(6), sm(7)
@@ -740,6 +768,16 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
                 raise ValueError(f"rasterize_backward_batch: every grad_depth image must hold H * W = {HW} elements")
             pre["scratch"] = [s if s.numel() >= sbytes(P, stt.num_rendered) else torch.empty((sbytes(P, stt.num_rendered),), dtype=torch.uint8, device=dev)
                               for s, stt in zip(pre["scratch"], states)]
+        ga = None
+        if grad_alpha is not None:
+            if states[0].raw_fused is not None:
+                raise RuntimeError("rasterize_backward_batch: grad_alpha is not supported with the fused raw-parameter activations")
+            HW = states[0].H * states[0].W
+            if isinstance(grad_alpha, torch.Tensor):
+                grad_alpha = [grad_alpha[v] for v in range(V)]
+            ga = [None if a is None else a.to(**f32).contiguous() for a in grad_alpha]
+            if any(a is not None and a.numel() != HW for a in ga):
+                raise ValueError(f"rasterize_backward_batch: every grad_alpha image must hold H * W = {HW} elements")
         d_means3D, d_means2D, d_colors, d_opacity = pre["d_means3D"], pre["d_means2D"], pre["d_colors"], pre["d_opacity"]
         d_scales, d_rot, d_cov, scratch = pre["d_scales"], pre["d_rot"], pre["d_cov"], pre["scratch"]
 
@@ -750,6 +788,19 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             #                      come back as the gradients of the UNACTIVATED parameters (same shapes)
             rawp = GsrRawParams(_ptr(fused[0]), None, None, _ptr(rotations), _ptr(states[0].act[1]), _ptr(scales),
                                 _ptr(d_rot), _ptr(d_opacity), _ptr(d_scales))
+        if ga is not None:
+            _check(lib.gsr_backward_batch_ext(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                              _ptr(None if per_view_col else colors_precomp),
+                                              _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),
+                                              _ptr_array([stt.binning for stt in states]), _ptr_array([stt.image for stt in states]),
+                                              _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
+                                              _ptr(d_means3D), per_view(d_means2D),
+                                              _ptr(None if (per_view_col or not want_color_grad) else d_colors),
+                                              per_view(d_colors) if (per_view_col and want_color_grad) else None,
+                                              _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
+                                              _ptr_array(gd) if grad_depth is not None else None, _ptr_array(ga), _stream(dev)),
+                   "gsr_backward_batch_ext")
+            return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
         if grad_depth is not None:
             _check(lib.gsr_backward_batch_depth(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
                                                 _ptr(None if per_view_col else colors_precomp),
@@ -1173,6 +1224,25 @@ def final_transmittance(state: RasterState) -> torch.Tensor:
     state is released or reused."""
     n = state.H * state.W
     return state.image[:4 * n].view(torch.float32).reshape(state.H, state.W)
+
+
+def rendered_alpha(states) -> torch.Tensor:
+    """[V,1,H,W] float32: the rendered alpha 1 - final_T of each forward state (gsr_alpha_views: one launch for all of them), bit for bit
+    the forward's own transmittance; zeros for P = 0."""
+    lib = load_library()
+    st0 = states[0]
+    V, H, W = len(states), st0.H, st0.W
+    dev = st0.image.device
+    if any(s.H != H or s.W != W for s in states):
+        raise ValueError("rendered_alpha: all states must share the image size")
+    if V > MAX_BATCH:
+        return torch.cat([rendered_alpha(states[lo:lo + MAX_BATCH]) for lo in range(0, V, MAX_BATCH)])
+    if st0.P == 0:
+        return torch.zeros((V, 1, H, W), dtype=torch.float32, device=dev)
+    with _on(dev):
+        out = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev)
+        _check(lib.gsr_alpha_views(V, H, W, _ptr_array([s.image for s in states]), _ptr(out), _stream(dev)), "gsr_alpha_views")
+    return out
 
 
 def debug_views(state: RasterState):

@@ -164,6 +164,23 @@ int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, 
                        const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream);
+/* gsr_backward with incoming gradients for the depth image AND the rendered alpha: dL_dalpha [1,H,W] (device) differentiates
+ * A = 1 - final_T (gsr_alpha_views).  dA/dalpha_i = final_T / (1 - alpha_i) has the background term's form, so the alpha gradient only
+ * adds final_T * dL_dalpha to that per-pixel term of the blend backward: it reaches dL_dmeans2D, the conic (dL_dscales, dL_drotations,
+ * dL_dcov3D), dL_dopacity and dL_dmeans3D, never dL_dcolors / dL_dsh.  The 0.99 clamp, the 1/255 cut and the T < 1e-4 stop are the
+ * forward's.  `scratch`: gsr_backward_scratch_bytes(P, num_rendered) when dL_ddepth is NULL, gsr_backward_scratch_bytes_depth otherwise
+ * (then gsr_backward_depth's rules hold).  dL_dalpha == NULL: exactly gsr_backward_depth (and with dL_ddepth NULL too, gsr_backward). */
+int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
+                     const float* dL_dalpha, void* stream);
+/* The rendered alpha of V forwards of one image size, one launch: out_alpha[v * H * W + pix] = 1 - final_T of image_states[v] (device,
+ * [V,H,W] contiguous), bit for bit the forward's own transmittance; 0 where nothing was blended.  Valid after any forward of those states
+ * (single view, shared lists, batch, capacity mode, fused pairs, forward-only, depth cuts).  V in 1..GSR_MAX_BATCH. */
+int gsr_alpha_views(int32_t V, int32_t H, int32_t W, void* const* image_states, float* out_alpha, void* stream);
 
 /* ---- multi-view batch (new design, no counterpart in the reference: its training loop renders one view per
  * optimiser step, /root/reference/src/tracking/train_gs.py:25-39).  The V views of a sharded step share the
@@ -297,6 +314,17 @@ int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const 
                              float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                              float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
                              void* stream);
+/* gsr_backward_batch with depth and alpha gradients (see gsr_backward_ext): dL_dalpha_views[V] device pointers to [1,H,W], a NULL entry
+ * = no alpha gradient for that view.  The depth rules are gsr_backward_batch_depth's; alpha alone keeps fused pairs fused (each view of a
+ * pair adds its own alpha term).  dL_dalpha_views == NULL: exactly gsr_backward_batch_depth. */
+int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                           const float* scales, const float* rotations, const float* colors_precomp,
+                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                           void* const* binning_states, void* const* image_states, void* batch_state,
+                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                           const float* const* dL_dalpha_views, void* stream);
 
 /* ---- neighbour terms of the t > 0 tracking loss, fused (caller side of the path):
  *   rigid, rot, iso of /root/reference/src/tracking/train_utils.py:198-222 as three means over (foreground point, neighbour).
