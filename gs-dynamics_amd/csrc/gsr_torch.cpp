@@ -270,8 +270,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
                              const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
-                             const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W] -> gsr_backward_depth
-                             const c10::optional<torch::Tensor>& dL_dout_alpha) {  // extension (default None): [1, H, W] -> gsr_backward_ext
+                             const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W], the depth build
+                             const c10::optional<torch::Tensor>& dL_dout_alpha) {  // extension (default None): [1, H, W], the alpha term
   const c10::Device dev = means3D.device();
   c10::hip::HIPGuard guard(dev.index());
   const int64_t P = means3D.size(0);
@@ -303,30 +303,21 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev);
   void* stream = (void*)c10::hip::getCurrentHIPStream(dev.index()).stream();
   auto optr = [](torch::Tensor& t) -> float* { return t.numel() ? t.data_ptr<float>() : nullptr; };
+  // the depth image's gradient (the depth build, its larger scratch) and the rendered alpha's: NULL when absent, both NULL is gsr_backward
   const bool has_depth = dL_dout_depth.has_value() && dL_dout_depth->defined();
   const bool has_alpha = dL_dout_alpha.has_value() && dL_dout_alpha->defined();
-  if (has_depth || has_alpha) {   // differentiable depth (the depth build, its larger scratch) and / or the rendered alpha's gradient
-    TORCH_CHECK(!has_depth || dL_dout_depth->numel() == H * W, "dL_dout_depth must hold H * W elements ([1, H, W])");
-    TORCH_CHECK(!has_alpha || dL_dout_alpha->numel() == H * W, "dL_dout_alpha must hold H * W elements ([1, H, W])");
-    const torch::Tensor gd = has_depth ? f32c(*dL_dout_depth, dev) : torch::Tensor(), ga = has_alpha ? f32c(*dL_dout_alpha, dev) : torch::Tensor();
-    torch::Tensor scratch = torch::empty({(int64_t)(has_depth ? gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)
-                                                               : gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R))},
-                                         torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-    check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
-                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
-                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
-                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
-                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
-          "gsr_backward_ext");
-    return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
-  }
-  torch::Tensor scratch = torch::empty({(int64_t)gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R)},
+  TORCH_CHECK(!has_depth || dL_dout_depth->numel() == H * W, "dL_dout_depth must hold H * W elements ([1, H, W])");
+  TORCH_CHECK(!has_alpha || dL_dout_alpha->numel() == H * W, "dL_dout_alpha must hold H * W elements ([1, H, W])");
+  const torch::Tensor gd = has_depth ? f32c(*dL_dout_depth, dev) : torch::Tensor(), ga = has_alpha ? f32c(*dL_dout_alpha, dev) : torch::Tensor();
+  torch::Tensor scratch = torch::empty({(int64_t)(has_depth ? gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)
+                                                             : gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R))},
                                        torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-  check(gsr_backward(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov), radii.data_ptr<int32_t>(),
-                     geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(), g.data_ptr<float>(),
-                     R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(), optr(d_colors),
-                     d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh), stream),
-        "gsr_backward");
+  check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                         radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                         g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                         optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
+                         has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
+        "gsr_backward_ext");
   return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
 }
 
@@ -414,7 +405,7 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
           const torch::Tensor& opacities, const torch::Tensor& scales, const torch::Tensor& rotations, const torch::Tensor& cov3D,
           const torch::Tensor& bg, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& campos,
           double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered,
-          bool differentiable_depth,     // extension: the depth output is differentiated too (gsr_backward_depth)
+          bool differentiable_depth,     // extension: the depth output is differentiated too (the depth build)
           bool return_alpha) {           // extension: a fourth output, the rendered alpha 1 - final_T (differentiable)
   bool will_backward = false;
   if (at::GradMode::is_enabled())

@@ -21,9 +21,10 @@ import os
 
 from . import _hip
 
-# The torch C++ layer (csrc/gsr_torch.cpp -> _C.so, built by __graft_entry__.build()): upstream's three entry points, one native call
-# per forward / backward.  Absent (not built) or switched off (GSR_NO_TORCH_EXT=1, or GSR_HIP_LIB pointing at another library
-# build, which _C is not linked against): the ctypes binding in _hip.py does the same work call by call.
+# The torch C++ layer (csrc/gsr_torch.cpp -> _C.so, built by __graft_entry__.build()): a single-view call is ONE native call,
+# _C.rasterize, whose autograd node is in C++.  Absent (not built) or switched off (GSR_NO_TORCH_EXT=1, or GSR_HIP_LIB pointing at
+# another library build, which _C is not linked against): the Python node _RasterizeGaussians over the ctypes binding in _hip.py
+# does the same work call by call.  Multi-view calls always take the ctypes binding.
 _C = None
 if os.environ.get("GSR_NO_TORCH_EXT") != "1" and "GSR_HIP_LIB" not in os.environ:
     try:
@@ -32,7 +33,7 @@ if os.environ.get("GSR_NO_TORCH_EXT") != "1" and "GSR_HIP_LIB" not in os.environ
     except ImportError:
         _C = None
 _CTYPES_FORWARD, _CTYPES_BACKWARD = _hip.rasterize_forward, _hip.rasterize_backward
-_PY_NODE = os.environ.get("GSR_PY_AUTOGRAD") == "1"   # A/B: the autograd node as a Python torch.autograd.Function (rounds 1 - 4) instead of _C.rasterize
+_PY_NODE = os.environ.get("GSR_PY_AUTOGRAD") == "1"   # A/B: the Python node over the ctypes binding instead of _C.rasterize
 
 
 _LAYER_STATES = {}     # device index -> _C.LayerState: what the torch C++ layer remembers between GaussianRasterizer calls on that device
@@ -94,8 +95,24 @@ def _prep(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return t.contiguous()
 
 
+def _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_):
+    """Which optional inputs the call had (``ctx.has``), and the inputs the backward needs (absent ones as empty placeholders)."""
+    ctx.has = (sh_ is not None, col_ is not None, sc_ is not None, cov_ is not None)
+    empty = m3.new_empty(0)
+    ctx.save_for_backward(m3, radii, *(empty if t is None else t for t in (col_, sh_, sc_, rot_, cov_)))
+    ctx.mark_non_differentiable(radii)
+
+
+def _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales, d_rot, d_cov):
+    """One gradient slot per apply() argument: None for the inputs the call did not have and for the settings and the two switches."""
+    has_sh, has_col, has_sc, has_cov = ctx.has
+    return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity, d_scales if has_sc else None,
+            d_rot if has_sc else None, d_cov if has_cov else None, None, None, None)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
-    """forward -> (color, radii, depth[, alpha]); backward -> grads for the 8 tensor inputs, None for settings."""
+    """One view over the ctypes binding: forward -> (color, radii, depth[, alpha]); backward -> grads for the 8 tensor inputs, None for
+    settings."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -117,36 +134,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         if m3.dim() != 2 or m3.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         ctx.empty = False
-        native = _native() if m3.is_cuda else None
-        if native is not None:
-            rs = raster_settings
-            e = m3.new_empty(0)
-            t = lambda x: e if (x is None or x.numel() == 0) else x   # noqa: E731
-            col_, sh_, sc_, rot_, cov_ = t(colors_precomp), t(sh), t(scales), t(rotations), t(cov3Ds_precomp)
-            D, color, depth, radii, geom, binning, image = native.rasterize_gaussians(
-                rs.bg, m3, col_, opacities, sc_, rot_, float(rs.scale_modifier), cov_, rs.viewmatrix, rs.projmatrix, float(rs.tanfovx),
-                float(rs.tanfovy), int(rs.image_height), int(rs.image_width), sh_, int(rs.sh_degree), rs.campos, bool(rs.prefiltered),
-                bool(any(ctx.needs_input_grad)), layer_state(m3.device))       # (only reached through the Python node: test doubles; under torch.no_grad() this still says True -- the C++ node decides before it is built)
-            ctx.native, ctx.rs, ctx.num_rendered = native, rs, int(D)
-            ctx.has = (sh_.numel() > 0, col_.numel() > 0, sc_.numel() > 0, cov_.numel() > 0)
-            ctx.save_for_backward(m3, radii, col_, sh_, sc_, rot_, cov_, geom, binning, image)
-            ctx.mark_non_differentiable(radii)
-            if ctx.alpha:     # 1 - final_T of this call's image state (the C++ layer's buffers have the library's layout)
-                st_ = _hip.RasterState()
-                st_.image, st_.H, st_.W, st_.P = image, int(rs.image_height), int(rs.image_width), int(m3.shape[0])
-                return color, radii, depth, _hip.rendered_alpha([st_])[0]
-            return color, radii, depth
-        ctx.native = None
         sh_, col_, op_ = _prep(sh), _prep(colors_precomp), _prep(opacities)
         sc_, rot_, cov_ = _prep(scales), _prep(rotations), _prep(cov3Ds_precomp)
         color, radii, depth, state = _hip.rasterize_forward(raster_settings, m3, op_, col_, sh_, sc_, rot_, cov_)
         ctx.state = state
-        ctx.has = (sh_ is not None, col_ is not None, sc_ is not None, cov_ is not None)
-        empty = m3.new_empty(0)
-        ctx.save_for_backward(m3, radii, col_ if col_ is not None else empty, sh_ if sh_ is not None else empty,
-                              sc_ if sc_ is not None else empty, rot_ if rot_ is not None else empty,
-                              cov_ if cov_ is not None else empty)
-        ctx.mark_non_differentiable(radii)
+        _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_)
         if ctx.alpha:
             return color, radii, depth, _hip.rendered_alpha([state])[0]
         return color, radii, depth
@@ -156,21 +148,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth; grad_alpha: used whenever autograd delivers one
         if ctx.empty:
             return (None,) * 11
-        if not ctx.depth:
-            grad_depth = None
-        if ctx.native is not None:
-            m3, radii, col_, sh_, sc_, rot_, cov_, geom, binning, image = ctx.saved_tensors
-            has_sh, has_col, has_sc, has_cov = ctx.has
-            rs = ctx.rs
-            if grad_color is None:
-                grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), device=m3.device)
-            d2, dc, do, d3, dcov, dsh, ds, dr = ctx.native.rasterize_gaussians_backward(
-                rs.bg, m3, radii, col_, sc_, rot_, float(rs.scale_modifier), cov_, rs.viewmatrix, rs.projmatrix, float(rs.tanfovx),
-                float(rs.tanfovy), grad_color, sh_, int(rs.sh_degree), rs.campos, geom, ctx.num_rendered, binning, image,
-                bool(has_col and ctx.needs_input_grad[3]),   # frozen colours (the reference's training): the six-sum backward
-                *(() if grad_depth is None else (grad_depth,)), **({} if grad_alpha is None else {"dL_dout_alpha": grad_alpha}))
-            return (d3, d2, dsh if has_sh else None, dc if (has_col and ctx.needs_input_grad[3]) else None, do, ds if has_sc else None, dr if has_sc else None,
-                    dcov if has_cov else None, None, None, None)
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         if grad_color is None:
@@ -178,10 +155,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh = _hip.rasterize_backward(
             ctx.state, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
-            want_color_grad=bool(has_col and ctx.needs_input_grad[3]), **({} if grad_depth is None else {"grad_depth": grad_depth}),
+            want_color_grad=bool(has_col and ctx.needs_input_grad[3]),
+            **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}),
             **({} if grad_alpha is None else {"grad_alpha": grad_alpha}))
-        return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity,
-                d_scales if has_sc else None, d_rot if has_sc else None, d_cov if has_cov else None, None, None, None)
+        return _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales, d_rot, d_cov)
 
 
 class _RasterizeGaussiansViews(torch.autograd.Function):
@@ -206,12 +183,7 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
                                                                    prepare_backward=wants_grad, **({} if wants_grad else {"forward_only": True}),
                                                                    **({"depth_scratch": True} if (ctx.depth and wants_grad) else {}))
         ctx.states = states
-        ctx.has = (sh_ is not None, col_ is not None, sc_ is not None, cov_ is not None)
-        empty = m3.new_empty(0)
-        ctx.save_for_backward(m3, radii, col_ if col_ is not None else empty, sh_ if sh_ is not None else empty,
-                              sc_ if sc_ is not None else empty, rot_ if rot_ is not None else empty,
-                              cov_ if cov_ is not None else empty)
-        ctx.mark_non_differentiable(radii)
+        _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_)
         if ctx.alpha:
             return color, radii, depth, _hip.rendered_alpha(states)
         return color, radii, depth
@@ -231,8 +203,7 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
             **({"grad_alpha": grad_alpha} if grad_alpha is not None else {}))
         # gradients arrive already summed over views (means2D stays per view); the state stays on ctx so that a
         # second backward (retain_graph=True) works, and is released with the graph
-        return (d3, d2, dsh if has_sh else None, dc if has_col else None, do, ds if has_sc else None,
-                dr if has_sc else None, dcov if has_cov else None, None, None, None)
+        return _input_grads(ctx, d3, d2, dsh, dc, do, ds, dr, dcov)
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
@@ -273,18 +244,15 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         raster_settings, differentiable_depth=False, return_alpha=False):
     """One view (upstream's entry point).  ``return_alpha``: a fourth output, the rendered alpha [1,H,W] (see GaussianRasterizer)."""
     native = _native() if (means3D is not None and means3D.is_cuda) else None
-    if native is not None and hasattr(native, "rasterize") and not _PY_NODE:
+    if native is not None and not _PY_NODE:
         # one crossing into the torch C++ layer: forward and the autograd node live there (csrc/gsr_torch.cpp: RasterizeFn)
         rs = raster_settings
         return native.rasterize(layer_state(means3D.device), means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg, rs.viewmatrix,
                                 rs.projmatrix, rs.campos, float(rs.tanfovx), float(rs.tanfovy), int(rs.image_height), int(rs.image_width),
                                 float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered),
-                                *((bool(differentiable_depth), True) if return_alpha else ((True,) if differentiable_depth else ())))
-    if differentiable_depth or return_alpha:
-        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha))
+                                differentiable_depth=bool(differentiable_depth), return_alpha=bool(return_alpha))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha))
 
 
 class GaussianRasterizer(nn.Module):
@@ -329,8 +297,5 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
-        if self.differentiable_depth or self.return_alpha:
-            return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs)
+                                   cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha)

@@ -368,8 +368,8 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
                        cov3D_precomp, want_color_grad: bool = True, grad_depth=None, grad_alpha=None):
     """K7..K9.  Returns (dmeans3D, dmeans2D, dcolors, dopacity[P,1], dscales, drotations, dcov3D, dsh).
     ``want_color_grad=False`` (precomputed colours that need no gradient): dcolors is None and the blend backward keeps six sums
-    per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (gsr_backward_depth); None is
-    exactly gsr_backward.  ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient (gsr_backward_ext); None adds nothing."""
+    per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (the depth build, its larger
+    scratch); ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient.  Both None is exactly gsr_backward."""
     lib = load_library()
     dev = means3D.device
     P, D = state.P, state.num_rendered
@@ -377,6 +377,11 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
     f32 = dict(dtype=torch.float32, device=dev)
     with _on(dev):
         g = grad_color.to(**f32).contiguous()
+        gd = None if grad_depth is None else grad_depth.to(**f32).contiguous()
+        ga = None if grad_alpha is None else grad_alpha.to(**f32).contiguous()
+        for name, t in (("grad_depth", gd), ("grad_alpha", ga)):
+            if t is not None and t.numel() != state.H * state.W:
+                raise ValueError(f"rasterize_backward: {name} must hold H * W = {state.H * state.W} elements ([1, H, W]), got {t.numel()}")
         d_means3D = torch.empty((P, 3), **f32)
         d_means2D = torch.empty((P, 3), **f32)
         d_colors = torch.empty((P, 3), **f32) if (shs is None and want_color_grad) else None
@@ -385,37 +390,13 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
         d_rot = torch.empty((P, 4), **f32) if cov3D_precomp is None else None
         d_cov = torch.empty((P, 6), **f32)
         d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
-        if grad_alpha is not None:
-            gd = None if grad_depth is None else grad_depth.to(**f32).contiguous()
-            ga = grad_alpha.to(**f32).contiguous()
-            for name, t in (("grad_depth", gd), ("grad_alpha", ga)):
-                if t is not None and t.numel() != state.H * state.W:
-                    raise ValueError(f"rasterize_backward: {name} must hold H * W = {state.H * state.W} elements ([1, H, W]), got {t.numel()}")
-            sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
-            scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
-            _check(lib.gsr_backward_ext(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                        _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
-                                        _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
-                                        _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
-                                        _ptr(d_cov), _ptr(d_sh), _ptr(gd), _ptr(ga), _stream(dev)), "gsr_backward_ext")
-            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
-        if grad_depth is not None:
-            gd = grad_depth.to(**f32).contiguous()
-            if gd.numel() != state.H * state.W:
-                raise ValueError(f"rasterize_backward: grad_depth must hold H * W = {state.H * state.W} elements ([1, H, W]), got {gd.numel()}")
-            scratch = torch.empty((lib.gsr_backward_scratch_bytes_depth(P, D),), dtype=torch.uint8, device=dev)
-            _check(lib.gsr_backward_depth(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                          _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
-                                          _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
-                                          _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
-                                          _ptr(d_cov), _ptr(d_sh), _ptr(gd), _stream(dev)), "gsr_backward_depth")
-            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
-        scratch = torch.empty((lib.gsr_backward_scratch_bytes(P, D),), dtype=torch.uint8, device=dev)
-        _check(lib.gsr_backward(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
-                                _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
-                                _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
-                                _ptr(d_cov), _ptr(d_sh), _stream(dev)), "gsr_backward")
+        sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
+        scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
+        _check(lib.gsr_backward_ext(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
+                                    _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
+                                    _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
+                                    _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
+                                    _ptr(d_cov), _ptr(d_sh), _ptr(gd), _ptr(ga), _stream(dev)), "gsr_backward_ext")
     return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
 
 
@@ -711,15 +692,28 @@ def forward_counts_ok(states) -> bool:
     return top <= cap_e
 
 
+def _view_images(images, states, name, f32):
+    """A per-view image gradient of rasterize_backward_batch -- [V,1,H,W], or a sequence of V images or None -- as a list of V
+    contiguous fp32 images or None entries; None when every entry is None."""
+    V, HW = len(states), states[0].H * states[0].W
+    if len(images) != V:
+        raise ValueError(f"rasterize_backward_batch: {name} must have one entry per view ({V})")
+    out = [None if t is None else t.to(**f32).contiguous() for t in images]
+    if all(t is None for t in out):
+        return None
+    if any(t is not None and t.numel() != HW for t in out):
+        raise ValueError(f"rasterize_backward_batch: every {name} image must hold H * W = {HW} elements")
+    return out
+
+
 def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp, shs, scales, rotations, cov3D_precomp,
                              want_color_grad: bool = True, grad_out=None, grad_depth=None, grad_alpha=None):
     """Backward of all views.  Returns gradients already SUMMED over views (dmeans3D[P,3], dcolors, dopacity[P,1],
     dscales, drotations, dcov3D, dsh) plus the per-view means2D gradients [V,P,3].
-    ``grad_depth`` ([V,1,H,W], or a sequence of V such images or None, or None): the depth images' gradient (gsr_backward_batch_depth:
-    views the forward fused into pairs are differentiated unfused; a None entry = no depth gradient for that view); None, or no image
-    at all, is exactly gsr_backward_batch.
-    ``grad_alpha`` (same forms): the rendered alphas' gradient (gsr_backward_batch_ext: fused pairs stay fused; a None entry = no alpha
-    gradient for that view); None, or no image at all, adds nothing."""
+    ``grad_depth`` ([V,1,H,W], or a sequence of V such images or None, or None): the depth images' gradient (views the forward fused
+    into pairs are differentiated unfused; a None entry = no depth gradient for that view).
+    ``grad_alpha`` (same forms): the rendered alphas' gradient (fused pairs stay fused; a None entry = no alpha gradient for that view).
+    None, or no image at all, for both is exactly gsr_backward_batch."""
     lib = load_library()
     dev = means3D.device
     V = len(states)
@@ -727,23 +721,18 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     if states[0].forward_only:
         raise RuntimeError("rasterize_backward_batch: these states come from a forward_only forward (no record-slot offsets were produced)")
     f32 = dict(dtype=torch.float32, device=dev)
-    if grad_depth is not None and not isinstance(grad_depth, torch.Tensor):
-        if len(grad_depth) != V:
-            raise ValueError(f"rasterize_backward_batch: grad_depth must have one entry per view ({V})")
-        if all(d is None for d in grad_depth):
-            grad_depth = None
-    if grad_alpha is not None and not isinstance(grad_alpha, torch.Tensor):
-        if len(grad_alpha) != V:
-            raise ValueError(f"rasterize_backward_batch: grad_alpha must have one entry per view ({V})")
-        if all(a is None for a in grad_alpha):
-            grad_alpha = None
+    gd = None if grad_depth is None else _view_images(grad_depth, states, "grad_depth", f32)
+    ga = None if grad_alpha is None else _view_images(grad_alpha, states, "grad_alpha", f32)
     if shs is not None:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
         outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp,
-                                   grad_depth=None if grad_depth is None else grad_depth[v],
-                                   grad_alpha=None if grad_alpha is None else grad_alpha[v])
+                                   grad_depth=None if gd is None else gd[v], grad_alpha=None if ga is None else ga[v])
                 for v in range(V)]
         sm = lambda k: None if outs[0][k] is None else torch.stack([o[k] for o in outs]).sum(0)  # noqa: E731
         return sm(0), torch.stack([o[1] for o in outs]), None, sm(3), sm(4), sm(5), sm(6), sm(7)
+    fused = states[0].raw_fused
+    if fused is not None and (gd is not None or ga is not None):
+        raise RuntimeError(f"rasterize_backward_batch: {'grad_depth' if gd is not None else 'grad_alpha'} is not supported with the fused "
+                           "raw-parameter activations")
     with _on(dev):
         g = grad_color.to(**f32).contiguous()
         sarr = (GsrSettings * V)()
@@ -754,77 +743,31 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
         per_view_col = colors_precomp is not None and colors_precomp.dim() == 3
         pre, states[0].pre = states[0].pre, None   # one use only: autograd may keep the returned tensors as .grad
         # the depth build's scratch: the records, then one float of dL/dz per entry (a forward told so -- depth_scratch -- sized it already)
-        sbytes = lib.gsr_backward_scratch_bytes_depth if grad_depth is not None else lib.gsr_backward_scratch_bytes
+        sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
         if pre is None:
             pre = _alloc_backward(dev, V, P, [sbytes(P, stt.num_rendered) for stt in states], cov3D_precomp is None, per_view_col, grad_out)
-        if grad_depth is not None:
-            if states[0].raw_fused is not None:
-                raise RuntimeError("rasterize_backward_batch: grad_depth is not supported with the fused raw-parameter activations")
-            HW = states[0].H * states[0].W
-            if isinstance(grad_depth, torch.Tensor):
-                grad_depth = [grad_depth[v] for v in range(V)]
-            gd = [None if d is None else d.to(**f32).contiguous() for d in grad_depth]
-            if any(d is not None and d.numel() != HW for d in gd):
-                raise ValueError(f"rasterize_backward_batch: every grad_depth image must hold H * W = {HW} elements")
+        elif gd is not None:
             pre["scratch"] = [s if s.numel() >= sbytes(P, stt.num_rendered) else torch.empty((sbytes(P, stt.num_rendered),), dtype=torch.uint8, device=dev)
                               for s, stt in zip(pre["scratch"], states)]
-        ga = None
-        if grad_alpha is not None:
-            if states[0].raw_fused is not None:
-                raise RuntimeError("rasterize_backward_batch: grad_alpha is not supported with the fused raw-parameter activations")
-            HW = states[0].H * states[0].W
-            if isinstance(grad_alpha, torch.Tensor):
-                grad_alpha = [grad_alpha[v] for v in range(V)]
-            ga = [None if a is None else a.to(**f32).contiguous() for a in grad_alpha]
-            if any(a is not None and a.numel() != HW for a in ga):
-                raise ValueError(f"rasterize_backward_batch: every grad_alpha image must hold H * W = {HW} elements")
         d_means3D, d_means2D, d_colors, d_opacity = pre["d_means3D"], pre["d_means2D"], pre["d_colors"], pre["d_opacity"]
         d_scales, d_rot, d_cov, scratch = pre["d_scales"], pre["d_rot"], pre["d_cov"], pre["scratch"]
 
         def per_view(t):
             return _ptr_array([t[v] for v in range(V)])
-        rawp, fused = None, states[0].raw_fused
+        args = (V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(None if per_view_col else colors_precomp),
+                _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]), _ptr_array([stt.binning for stt in states]),
+                _ptr_array([stt.image for stt in states]), _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
+                _ptr(d_means3D), per_view(d_means2D), _ptr(None if (per_view_col or not want_color_grad) else d_colors),
+                per_view(d_colors) if (per_view_col and want_color_grad) else None)
         if fused is not None:    # the chain through the activations runs inside the per-Gaussian kernel: d_rot / d_opacity / d_scales
             #                      come back as the gradients of the UNACTIVATED parameters (same shapes)
             rawp = GsrRawParams(_ptr(fused[0]), None, None, _ptr(rotations), _ptr(states[0].act[1]), _ptr(scales),
                                 _ptr(d_rot), _ptr(d_opacity), _ptr(d_scales))
-        if ga is not None:
-            _check(lib.gsr_backward_batch_ext(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                              _ptr(None if per_view_col else colors_precomp),
-                                              _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),
-                                              _ptr_array([stt.binning for stt in states]), _ptr_array([stt.image for stt in states]),
-                                              _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
-                                              _ptr(d_means3D), per_view(d_means2D),
-                                              _ptr(None if (per_view_col or not want_color_grad) else d_colors),
-                                              per_view(d_colors) if (per_view_col and want_color_grad) else None,
-                                              _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
-                                              _ptr_array(gd) if grad_depth is not None else None, _ptr_array(ga), _stream(dev)),
-                   "gsr_backward_batch_ext")
-            return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
-        if grad_depth is not None:
-            _check(lib.gsr_backward_batch_depth(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                                _ptr(None if per_view_col else colors_precomp),
-                                                _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),
-                                                _ptr_array([stt.binning for stt in states]), _ptr_array([stt.image for stt in states]),
-                                                _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
-                                                _ptr(d_means3D), per_view(d_means2D),
-                                                _ptr(None if (per_view_col or not want_color_grad) else d_colors),
-                                                per_view(d_colors) if (per_view_col and want_color_grad) else None,
-                                                _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), _ptr_array(gd), _stream(dev)),
-                   "gsr_backward_batch_depth")
-            return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
-        _check(lib.gsr_backward_batch_raw(V, sarr, P, Ds, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                          _ptr(None if per_view_col else colors_precomp),
-                                          _ptr(cov3D_precomp), per_view(radii), _ptr_array([stt.geom for stt in states]),
-                                          _ptr_array([stt.binning for stt in states]), _ptr_array([stt.image for stt in states]),
-                                          _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch), _ptr(d_means3D),
-                                          per_view(d_means2D),
-                                          _ptr(None if (per_view_col or not want_color_grad) else d_colors),
-                                          per_view(d_colors) if (per_view_col and want_color_grad) else None,
-                                          _ptr(None if fused is not None else d_opacity), _ptr(None if fused is not None else d_scales),
-                                          _ptr(None if fused is not None else d_rot), _ptr(d_cov),
-                                          C.byref(rawp) if rawp is not None else None, _stream(dev)),
-               "gsr_backward_batch")
+            rc = lib.gsr_backward_batch_raw(*args, None, None, None, _ptr(d_cov), C.byref(rawp), _stream(dev))
+        else:
+            rc = lib.gsr_backward_batch_ext(*args, _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
+                                            None if gd is None else _ptr_array(gd), None if ga is None else _ptr_array(ga), _stream(dev))
+        _check(rc, "gsr_backward_batch")
     # without a colour gradient, views that share a camera stay fused in the backward (one replay of the tile lists for both)
     return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
 

@@ -334,8 +334,8 @@ def test_producer_consumer_build(tmp_path):
 
 
 def test_backends_agree(dev, monkeypatch):
-    """The three single-view paths -- the C++ node, the Python node over the C++ layer's functions, the Python node over the ctypes binding
-    (forced by a spy on the ctypes forward) -- give the same alpha and the same gradients of a colour + alpha loss."""
+    """The two single-view backends -- the C++ node, and the Python node over the ctypes binding, chosen by the switch and forced by a spy
+    on the ctypes forward -- give the same alpha and the same gradients of a colour + alpha loss."""
     import diff_gaussian_rasterization as dgr
     from diff_gaussian_rasterization import _hip as hip
     P, W, H = 2500, 150, 110
@@ -344,7 +344,10 @@ def test_backends_agree(dev, monkeypatch):
     dLc, dLa = _loss_images(cam, 28, np.ones((H, W), bool))
     runs = [_hip(cam, g, dev, dLc, dLa)]
     monkeypatch.setattr(dgr, "_PY_NODE", True)
+    bwd = _spy(monkeypatch, "rasterize_backward")
     runs.append(_hip(cam, g, dev, dLc, dLa))
+    assert bwd["kw"].get("grad_alpha") is not None, "the switch did not run the ctypes backward with an alpha gradient"
+    monkeypatch.setattr(dgr, "_PY_NODE", False)
     orig, called = hip.rasterize_forward, []
 
     def spy(*a, **k):
@@ -508,9 +511,10 @@ def _plain(cam, g, dev, dLc, frozen, alpha_out, zero_alpha_grad=False):
 @pytest.mark.parametrize("pynode", [False, True])
 def test_default_unchanged(dev, monkeypatch, pynode):
     """return_alpha=False against return_alpha=True with alpha unused, and with a zero alpha gradient: outputs and every gradient bit for
-    bit; the same for a batch call."""
+    bit; the same for a batch call.  pynode: the Python node over the ctypes binding."""
     import diff_gaussian_rasterization as dgr
     monkeypatch.setattr(dgr, "_PY_NODE", pynode)
+    bwd = _spy(monkeypatch, "rasterize_backward") if pynode else None
     P, W, H = 2000, 130, 94
     g = random_gaussians(P, seed=63, scale_lo=0.02, scale_hi=0.25)
     cam = ring_camera(W, H, v=3, bg=(0.1, 0.3, 0.5))
@@ -523,6 +527,8 @@ def test_default_unchanged(dev, monkeypatch, pynode):
             assert set(run[1]) == set(base[1])
             for k in base[1]:
                 assert np.array_equal(run[1][k], base[1][k]), k
+    if pynode:
+        assert "out" in bwd, "the Python node did not run the ctypes backward"
     cams = [ring_camera(W, H, v=v, V=4) for v in range(4)]
     dLcv = np.random.default_rng(65).uniform(-1, 1, (4, 3, H, W)).astype(np.float32)
     base = _views_call(cams, g, dev, dLcv, None, alpha=False)

@@ -256,7 +256,11 @@ def test_self_consistency_single_view(dev, monkeypatch, pynode):
     dLc = rng.uniform(-1, 1, (1, 3, H, W)).astype(np.float32)
     dLd = rng.uniform(-1, 1, (1, 1, H, W)).astype(np.float32)
     ref = _self_consistency_ref([cam], g, dev, dLc, dLd)
+    if pynode:
+        bwd = _spy(monkeypatch, "rasterize_backward")
     _, _, got = _hip(cam, g, dev, dLc[0], dLd[0], frozen=("colors_precomp",))
+    if pynode:
+        assert bwd["kw"].get("grad_depth") is not None, "the Python node did not run the ctypes backward with a depth gradient"
     for k in ("means3D", "opacities", "scales", "rotations"):
         _close_to_max(f"self-consistency {k}", got[k], ref[k])
     _close_to_max("self-consistency means2D", got["means2D"], ref["means2D"][0])
@@ -308,7 +312,7 @@ def _spy(monkeypatch, name, rewrite=None):
 
 
 def _depth_only_for(views):
-    """A rasterize_backward_batch rewrite: NULL depth gradient (None) for every view not in ``views`` (gsr_backward_batch_depth's NULL
+    """A rasterize_backward_batch rewrite: NULL depth gradient (None) for every view not in ``views`` (gsr_backward_batch_ext's NULL
     entries; autograd itself always hands the whole [V,1,H,W] image)."""
     def rw(k):
         gd = k.get("grad_depth")
@@ -341,7 +345,7 @@ def test_multiview_equals_sum_of_single_views(dev):
 
 
 def test_multiview_null_depth_entries(dev, monkeypatch):
-    """gsr_backward_batch_depth with NULL entries for the views without a depth loss (views 1 and 3): those views take no depth term in
+    """gsr_backward_batch_ext with NULL depth entries for the views without a depth loss (views 1 and 3): those views take no depth term in
     the per-Gaussian backward; the result equals the sum of the single-view calls."""
     P, W, H, V = 3000, 160, 120, 4
     g = random_gaussians(P, seed=12, scale_lo=0.02, scale_hi=0.25)
@@ -392,9 +396,11 @@ def test_multiview_fused_pairs_run_unfused(dev, monkeypatch, depth_views):
 
 @pytest.mark.parametrize("pynode", [False, True])
 def test_default_unchanged(dev, monkeypatch, pynode):
-    """differentiable_depth=False with a depth loss, and True without one: every output and gradient equals a call without the keyword."""
+    """differentiable_depth=False with a depth loss, and True without one: every output and gradient equals a call without the keyword.
+    pynode: the Python node over the ctypes binding."""
     import diff_gaussian_rasterization as dgr
     monkeypatch.setattr(dgr, "_PY_NODE", pynode)
+    bwd = _spy(monkeypatch, "rasterize_backward") if pynode else None
     P, W, H = 2000, 130, 94
     g = random_gaussians(P, seed=3, scale_lo=0.02, scale_hi=0.25)
     cam = ring_camera(W, H, v=3, bg=(0.1, 0.3, 0.5))
@@ -409,6 +415,8 @@ def test_default_unchanged(dev, monkeypatch, pynode):
             assert set(run[2]) == set(base[2])
             for k in base[2]:
                 assert np.array_equal(run[2][k], base[2][k]), k
+    if pynode:
+        assert "out" in bwd, "the Python node did not run the ctypes backward"
     cams = [ring_camera(W, H, v=v, V=4) for v in range(4)]
     dLcv = rng.uniform(-1, 1, (4, 3, H, W)).astype(np.float32)
     dLdv = rng.uniform(-1, 1, (4, 1, H, W)).astype(np.float32)
