@@ -80,6 +80,11 @@ static int make_cam(const gsr_settings* s, GsrCam* c) {
   c->tanfovx = s->tanfovx; c->tanfovy = s->tanfovy; c->scale_modifier = s->scale_modifier;
   c->sh_degree = s->sh_degree; c->M = s->sh_coeffs;
   c->bg = s->bg; c->view = s->viewmatrix; c->proj = s->projmatrix; c->campos = s->campos;
+  if (s->prefiltered & ~(int32_t)(1 | GSR_SETTINGS_ANTIALIASING)) {
+    gsr_set_error("gsr: unknown bits 0x%x in settings.prefiltered (bit 0: prefiltered, bit 1: GSR_SETTINGS_ANTIALIASING)", (unsigned)s->prefiltered);
+    return -2;
+  }
+  c->antialiasing = (s->prefiltered & GSR_SETTINGS_ANTIALIASING) ? 1 : 0;
   return 0;
 }
 
@@ -608,6 +613,11 @@ size_t gsr_batch_state_bytes(int32_t V, int32_t P, int32_t H, int32_t W) { Batch
 static int check_batch(const char* who, int32_t V, const gsr_settings* s, const void* batch_state) {
   if (V <= 0 || V > GSR_MAX_BATCH) { gsr_set_error("%s: V must be in 1..%d", who, GSR_MAX_BATCH); return -2; }
   if (!s || !batch_state) { gsr_set_error("%s: NULL settings / batch_state", who); return -2; }
+  for (int v = 1; v < V; ++v)   // one preprocess launch (and one per-Gaussian backward) serves all views of a call
+    if ((s[v].prefiltered & GSR_SETTINGS_ANTIALIASING) != (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING)) {
+      gsr_set_error("%s: view %d's GSR_SETTINGS_ANTIALIASING differs from view 0's: all views of a call must agree", who, v);
+      return -2;
+    }
   return 0;
 }
 
@@ -833,6 +843,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
   bool depth = false;   // a depth gradient for some view: the depth build, which has no fused pairs (the call runs unfused)
   for (int v = 0; dL_ddepth_views && v < V; ++v) depth = depth || dL_ddepth_views[v] != nullptr;
   GsrDepthViews dv;
+  GsrAaViews av;          // anti-aliasing: every view's records (staged o'); check_batch made the views agree on the bit
+  const bool aa = (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING) != 0;
   const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth;
   if (!fuse_bwd)
     for (int v = 0; v < V; ++v) { partner[v] = -1; fused[v] = 0; }
@@ -864,6 +876,7 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
     w.fused_alias = fused[v];
     w.cap = num_rendered[v];
     w.W = cam.W; w.H = cam.H; w.tanfovx = cam.tanfovx; w.tanfovy = cam.tanfovy;
+    av.rec[v] = g.rec;
     if (depth) {   // every view's scratch holds gsr_backward_scratch_bytes_depth(P, num_rendered[v]): the blend writes dL/dz for all of them
       dv.dL_ddepth[v] = dL_ddepth_views[v];
       dv.dL_dz[v] = num_rendered[v] > 0 ? (float*)((char*)scratch[v] + gsr_depth_scratch_offset(num_rendered[v])) : nullptr;
@@ -886,7 +899,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
   }
   (void)colors_precomp;
   return gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
-                                         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st, (depth && any) ? &dvp : nullptr);
+                                         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st, (depth && any) ? &dvp : nullptr,
+                                         aa ? &av : nullptr);
 }
 extern "C" {
 

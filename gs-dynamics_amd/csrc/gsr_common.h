@@ -178,6 +178,7 @@ struct GsrCam {  // host copy of the scalar settings; matrices stay on the devic
   float tanfovx, tanfovy, scale_modifier;
   int sh_degree, M;
   const float *bg, *view, *proj, *campos;
+  int antialiasing;   // GSR_SETTINGS_ANTIALIASING: opacity compensation in the preprocess and its gradient
 };
 
 // Every stage is ONE launch for all V views of a call (V = 1 for the single-view entry points): a kernel finds
@@ -338,10 +339,14 @@ struct GsrBwdViews {
   float *d_raw_rot, *d_raw_op, *d_raw_sc;
   GsrBwdView v[GSR_MAX_BATCH];
 };
+// Anti-aliasing (GsrCam::antialiasing): every view's record array, whose staged opacity o' = o c the per-Gaussian backward reads
+struct GsrAaViews { const float4* rec[GSR_MAX_BATCH]; };
+static_assert(sizeof(GsrBwdViews) + sizeof(GsrDepthViews) + sizeof(GsrAaViews) + 128 <= 4096, "preprocess_bwd_views kernel arguments above 4 KB");
 int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_modifier, const float* means3D,
                                     const float* scales, const float* rotations, const float* cov3D_precomp,
                                     float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
-                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth = nullptr);
+                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth = nullptr,
+                                    const GsrAaViews* aa = nullptr);
 int gsr_launch_image_loss_fwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, float* fA,
                               float* fC, float* fE, float* block_l1, float* block_ssim, hipStream_t st);
 int gsr_launch_image_loss_bwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, const float* fA,
@@ -611,6 +616,19 @@ __device__ __forceinline__ float4 gsr_act_rotation_bwd(float4 q, float4 dr) {
   }
   return make_float4(dr.x * 1e12f, dr.y * 1e12f, dr.z * 1e12f, dr.w * 1e12f);   // clamped denominator: a constant
 }
+
+// ---- anti-aliasing (GSR_SETTINGS_ANTIALIASING): the staged opacity is o * c, c = sqrt(max(det0 / det1, floor)),
+// det0 = A C - B^2 of the projected covariance before the 0.3 px^2 dilation, det1 the dilated det the conic uses.  det0 is a difference of
+// nearly equal products for thin Gaussians: it is formed with Kahan's fma product difference (exact up to the final rounding).  One
+// definition for the forward and for the backward's recomputation of the forward's floor decision (both files build without contraction;
+// the fmas are explicit, so the bits do not depend on that flag).
+#define GSR_AA_FLOOR 2.5e-5f
+__device__ __forceinline__ float gsr_aa_ratio(float A, float B, float C, float det1) {
+  const float w = B * B;
+  const float e = fmaf(-B, B, w);          // w - B^2, exactly
+  return (fmaf(A, C, -w) + e) / det1;
+}
+__device__ __forceinline__ float gsr_aa_comp(float r) { return sqrtf(fmaxf(r, GSR_AA_FLOOR)); }
 
 // exp(x) for x <= 0: v_exp_f32 on x * log2(e) -- two VALU issues.  Relative error ~ |x| * 6e-8 + 1 ulp (|x| <= 5.6 wherever
 // alpha >= 1/255).  A compensated form (exact product error folded back in, ~1-2 ulp, 7 issues) was used until the parity

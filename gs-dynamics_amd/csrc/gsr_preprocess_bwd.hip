@@ -176,15 +176,66 @@ __device__ __forceinline__ void build_cov3(int i, float mod, const float* __rest
   o.c[5] = Mm[2][0] * Mm[2][0] + Mm[2][1] * Mm[2][1] + Mm[2][2] * Mm[2][2];
 }
 
+// Anti-aliasing builds: the forward's fp32 3D covariance, with its operations in its order (both files build with
+// contraction off, so these are its bits; raw-parameter mode: `scales` / `rotations` are the activated values that forward wrote).
+__device__ __forceinline__ void build_cov3_f32(int i, float mod, const float* __restrict__ scales, const float* __restrict__ rotations,
+                                               const float* __restrict__ cov3D_precomp, float c[6]) {
+  if (cov3D_precomp) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = cov3D_precomp[6 * i + k];
+    return;
+  }
+  const float r = rotations[4 * i], x = rotations[4 * i + 1], y = rotations[4 * i + 2], z = rotations[4 * i + 3];
+  const float R00 = 1.f - 2.f * (y * y + z * z), R01 = 2.f * (x * y - r * z), R02 = 2.f * (x * z + r * y);
+  const float R10 = 2.f * (x * y + r * z), R11 = 1.f - 2.f * (x * x + z * z), R12 = 2.f * (y * z - r * x);
+  const float R20 = 2.f * (x * z - r * y), R21 = 2.f * (y * z + r * x), R22 = 1.f - 2.f * (x * x + y * y);
+  const float s0 = mod * scales[3 * i], s1 = mod * scales[3 * i + 1], s2 = mod * scales[3 * i + 2];
+  const float M00 = R00 * s0, M01 = R01 * s1, M02 = R02 * s2;
+  const float M10 = R10 * s0, M11 = R11 * s1, M12 = R12 * s2;
+  const float M20 = R20 * s0, M21 = R21 * s1, M22 = R22 * s2;
+  c[0] = M00 * M00 + M01 * M01 + M02 * M02;
+  c[1] = M00 * M10 + M01 * M11 + M02 * M12;
+  c[2] = M00 * M20 + M01 * M21 + M02 * M22;
+  c[3] = M10 * M10 + M11 * M11 + M12 * M12;
+  c[4] = M10 * M20 + M11 * M21 + M12 * M22;
+  c[5] = M20 * M20 + M21 * M21 + M22 * M22;
+}
+// ... and the forward's fp32 ratio r = det0 / det1 of one view (gsr_aa_ratio), from the forward's view-space position: the side of the
+// floor the forward took.  An fp64 r within rounding of the floor could fall on the other side.
+__device__ __forceinline__ float aa_ratio32(const float* __restrict__ view, int W, int H, float tanfovx, float tanfovy, float pvz,
+                                            float txtz, float tytz, const float c[6]) {
+  const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
+  const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
+  const float tz = pvz;
+  const float tx = clampf(txtz, -limx, limx) * tz;
+  const float ty = clampf(tytz, -limy, limy) * tz;
+  const float J00 = fx / tz, J02 = -(fx * tx) / (tz * tz);
+  const float J11 = fy / tz, J12 = -(fy * ty) / (tz * tz);
+  const float T00 = J00 * view[0] + J02 * view[2], T01 = J00 * view[4] + J02 * view[6], T02 = J00 * view[8] + J02 * view[10];
+  const float T10 = J11 * view[1] + J12 * view[2], T11 = J11 * view[5] + J12 * view[6], T12 = J11 * view[9] + J12 * view[10];
+  const float U00 = T00 * c[0] + T01 * c[1] + T02 * c[2], U01 = T00 * c[1] + T01 * c[3] + T02 * c[4], U02 = T00 * c[2] + T01 * c[4] + T02 * c[5];
+  const float U10 = T10 * c[0] + T11 * c[1] + T12 * c[2], U11 = T10 * c[1] + T11 * c[3] + T12 * c[4], U12 = T10 * c[2] + T11 * c[4] + T12 * c[5];
+  float a = U00 * T00 + U01 * T01 + U02 * T02;
+  const float b = U00 * T10 + U01 * T11 + U02 * T12;
+  float cc = U10 * T10 + U11 * T11 + U12 * T12;
+  const float a0 = a, c0 = cc;
+  a += 0.3f; cc += 0.3f;
+  const float det = a * cc - b * b;
+  return gsr_aa_ratio(a0, b, c0, det);
+}
+
 // One view's chain: conic -> cov2D -> (cov3D, view-space mean) and 2D mean -> 3D mean.  ACCUMULATES into
 // gcov[6] and gm3[3]; returns this view's dL/d(NDC mean) in gm2.
 // DEPTH: gz = dL/d(view-space depth) of the Gaussian from the depth image; depth IS tz (no frustum clamp on it), so it joins dL/dtz and
 // reaches dL/dmeans3D as gz * (view[2], view[6], view[10]) inside the fp64 sum.
-template <bool DEPTH = false>
+// AA: the staged opacity was o' = o c(A, B, C).  c32 = the forward's fp32 3D covariance (build_cov3_f32), o_s = this
+// view's staged o'; the term o g dc/d{A, B, C} (g = ps.gop = dL/do') joins dL/d{a, b, c}, and *c_out receives the factor of dL/do = c g.
+template <bool DEPTH = false, bool AA = false>
 __device__ __forceinline__ void view_chain(const float* __restrict__ view, const float* __restrict__ proj, int W, int H,
                                            float tanfovx, float tanfovy, float3 p, const real c[6],
                                            const PartialSum& ps, float gcov[6], float gm3[3], float gm2[2],
-                                           float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr, float gz = 0.f) {
+                                           float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr, float gz = 0.f,
+                                           const float* c32 = nullptr, float o_s = 0.f, float* c_out = nullptr) {
   // The frustum clamp is the forward's decision: the fp32 view-space position, txtz / tytz and limit, with the forward's operations in its
   // order (both files build with contraction off, so these are its bits).  An fp64 txtz within ~1e-7 of the limit can fall on the other
   // side, and then dtx / dty would be dropped or added in full.  A clamped coordinate sits at the forward's fp32 limit, widened.
@@ -220,9 +271,34 @@ __device__ __forceinline__ void view_chain(const float* __restrict__ view, const
   const real det = a * cc - b * b;
   const real d2inv = 1.0f / (det * det + 0.0000001f);
   const real gA = ps.gA, gB = ps.gB, gC = ps.gC;
-  const real dL_da = d2inv * (-cc * cc * gA + b * cc * gB - b * b * gC);
-  const real dL_dc = d2inv * (-b * b * gA + a * b * gB - a * a * gC);
-  const real dL_db = d2inv * (2.0f * b * cc * gA - (det + 2.0f * b * b) * gB + 2.0f * a * b * gC);
+  const real dL_da0 = d2inv * (-cc * cc * gA + b * cc * gB - b * b * gC);
+  const real dL_dc0 = d2inv * (-b * b * gA + a * b * gB - a * a * gC);
+  const real dL_db0 = d2inv * (2.0f * b * cc * gA - (det + 2.0f * b * b) * gB + 2.0f * a * b * gC);
+  real aa_a = 0.0, aa_b = 0.0, aa_c = 0.0;
+  if (AA) {
+    // The floor decision is the forward's (fp32 r, its operations).  Floored: c is a constant, dL/do = c g and no covariance term.
+    // Otherwise, with A, C the undilated diagonal (a = A + h, cc = C + h), D = det and r = (A C - b^2) / D, the cancellation-free
+    //   dr/dA = h (C^2 + h C + b^2) / D^2,  dr/dC = h (A^2 + h A + b^2) / D^2,  dr/db = -2 h b (A + C + h) / D^2
+    // and o dc = o dr / (2 c); o = o' / c32 (the forward's c: o' = fl(o c32)).
+    const float r32 = aa_ratio32(view, W, H, tanfovx, tanfovy, pvz32, txtz32, tytz32, c32);
+    const float cf = gsr_aa_comp(r32);
+    if (r32 < GSR_AA_FLOOR) {
+      *c_out = cf;
+    } else {
+      const real h = (real)0.3f;
+      const real A = U0[0] * T0[0] + U0[1] * T0[1] + U0[2] * T0[2];
+      const real C = U1[0] * T1[0] + U1[1] * T1[1] + U1[2] * T1[2];
+      const real cr = sqrt(fmax((A * C - b * b) / det, (real)GSR_AA_FLOOR));
+      *c_out = (float)cr;
+      const real k = (real)o_s / (real)cf * (real)ps.gop / (2.0 * cr * det * det);
+      aa_a = k * h * (C * C + h * C + b * b);
+      aa_c = k * h * (A * A + h * A + b * b);
+      aa_b = -2.0 * k * h * b * (A + C + h);
+    }
+  }
+  const real dL_da = AA ? dL_da0 + aa_a : dL_da0;
+  const real dL_dc = AA ? dL_dc0 + aa_c : dL_dc0;
+  const real dL_db = AA ? dL_db0 + aa_b : dL_db0;
   gcov[0] += (float)(T0[0] * T0[0] * dL_da + T0[0] * T1[0] * dL_db + T1[0] * T1[0] * dL_dc);
   gcov[3] += (float)(T0[1] * T0[1] * dL_da + T0[1] * T1[1] * dL_db + T1[1] * T1[1] * dL_dc);
   gcov[5] += (float)(T0[2] * T0[2] * dL_da + T0[2] * T1[2] * dL_db + T1[2] * T1[2] * dL_dc);
@@ -294,14 +370,25 @@ __device__ __forceinline__ bool gsr_view_used(const GsrBwdView& w, int i) {
   return !w.used || !w.tracked || *w.tracked == 0u || w.used[i] != 0;
 }
 
-// The three kernels are written once (gsr_preprocess_bwd_kernels.inc) and compiled twice: GSR_PBWD_DEPTH 0 gives the kernels of
-// gsr_backward / gsr_backward_batch, 1 their differentiable-depth builds (*_depth_kernel: one more argument, the per-entry dL/dz).
+// The three kernels are written once (gsr_preprocess_bwd_kernels.inc) and compiled four times: GSR_PBWD_DEPTH 0 gives the kernels of
+// gsr_backward / gsr_backward_batch, 1 their differentiable-depth builds (*_depth_kernel: one more argument, the per-entry dL/dz);
+// GSR_PBWD_AA 1 the anti-aliasing builds of both (*_aa_kernel, *_aa_depth_kernel: one more argument, the staged records).
+#define GSR_PBWD_AA 0
 #define GSR_PBWD_DEPTH 0
 #include "gsr_preprocess_bwd_kernels.inc"
 #undef GSR_PBWD_DEPTH
 #define GSR_PBWD_DEPTH 1
 #include "gsr_preprocess_bwd_kernels.inc"
 #undef GSR_PBWD_DEPTH
+#undef GSR_PBWD_AA
+#define GSR_PBWD_AA 1
+#define GSR_PBWD_DEPTH 0
+#include "gsr_preprocess_bwd_kernels.inc"
+#undef GSR_PBWD_DEPTH
+#define GSR_PBWD_DEPTH 1
+#include "gsr_preprocess_bwd_kernels.inc"
+#undef GSR_PBWD_DEPTH
+#undef GSR_PBWD_AA
 
 }  // namespace gsr_preprocess_bwd
 using namespace gsr_preprocess_bwd;
@@ -319,7 +406,13 @@ int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, co
       cam.campos, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, g.offsets, g.clamped,  \
       partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dsh, g.used, g.counters + 1, bwd_error
   if (shs && !dL_dsh) { gsr_set_error("gsr_backward: shs given but dL_dsh is NULL"); return -2; }
-  if (dL_dz) {   // differentiable depth (gsr_backward_depth)
+  if (cam.antialiasing) {   // anti-aliasing builds: one more argument, the forward's records (staged o')
+    { GSR_PROF(dL_dz ? "preprocess_bwd_aa_depth" : "preprocess_bwd_aa", st);
+      if (dL_dz && shs) hipLaunchKernelGGL(preprocess_bwd_aa_depth_kernel<true>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz, g.rec);
+      else if (dL_dz) hipLaunchKernelGGL(preprocess_bwd_aa_depth_kernel<false>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz, g.rec);
+      else if (shs) hipLaunchKernelGGL(preprocess_bwd_aa_kernel<true>, grid, block, 0, st, GSR_PBWD_ARGS, g.rec);
+      else hipLaunchKernelGGL(preprocess_bwd_aa_kernel<false>, grid, block, 0, st, GSR_PBWD_ARGS, g.rec); }
+  } else if (dL_dz) {   // differentiable depth (gsr_backward_depth)
     { GSR_PROF("preprocess_bwd_depth", st);
       if (shs) hipLaunchKernelGGL(preprocess_bwd_depth_kernel<true>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz);
       else hipLaunchKernelGGL(preprocess_bwd_depth_kernel<false>, grid, block, 0, st, GSR_PBWD_ARGS, dL_dz); }
@@ -338,10 +431,37 @@ int gsr_launch_preprocess_bwd(const GsrCam& cam, int P, const float* means3D, co
 int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_modifier, const float* means3D,
                                     const float* scales, const float* rotations, const float* cov3D_precomp,
                                     float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
-                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth) {
+                                    float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth, const GsrAaViews* aa) {
   if (P <= 0) return 0;
   int nact = 0;
   for (int v = 0; v < vw.V; ++v) nact += vw.v[v].fused_alias ? 0 : 1;
+  if (aa) {   // anti-aliasing builds: the same launch shapes, one more argument (the views' records)
+    GSR_PROF("preprocess_bwd_views_aa", st);
+    const GsrAaViews& a = *aa;
+    if (nact >= 2) {
+#define PBW_AA_LAUNCH(K, MAXW, ...) hipLaunchKernelGGL(K<MAXW>, dim3((P + 63) / 64), dim3(64 * nact),                                     \
+                           sizeof(float) * (size_t)nact * (PBW_VALUES + 1) * 64, st, vw, P, scale_modifier, means3D, scales, rotations,       \
+                           cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, __VA_ARGS__)
+      if (depth) {
+        if (nact <= 4) PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_depth_kernel, 4, *depth, a);
+        else if (nact <= 8) PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_depth_kernel, 8, *depth, a);
+        else PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_depth_kernel, GSR_MAX_BATCH, *depth, a);
+      } else if (nact <= 4) PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_kernel, 4, a);
+      else if (nact <= 8) PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_kernel, 8, a);
+      else PBW_AA_LAUNCH(preprocess_bwd_views_waves_aa_kernel, GSR_MAX_BATCH, a);
+#undef PBW_AA_LAUNCH
+    } else if (depth) {
+      hipLaunchKernelGGL(preprocess_bwd_views_aa_depth_kernel, dim3((P + GSR_BLOCK - 1) / GSR_BLOCK), dim3(GSR_BLOCK), 0, st, vw, P,
+                         scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, *depth, a);
+    } else {
+      hipLaunchKernelGGL(preprocess_bwd_views_aa_kernel, dim3((P + GSR_BLOCK - 1) / GSR_BLOCK), dim3(GSR_BLOCK), 0, st, vw, P,
+                         scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, a);
+    }
+    GSR_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   if (nact >= 2) {      // one wave per view
     { GSR_PROF("preprocess_bwd_views", st);
 #define PBW_LAUNCH(MAXW) hipLaunchKernelGGL(preprocess_bwd_views_waves_kernel<MAXW>, dim3((P + 63) / 64), dim3(64 * nact),              \

@@ -1,16 +1,34 @@
-// gsr_preprocess_bwd_kernels.inc -- the per-Gaussian backward kernels, included twice by gsr_preprocess_bwd.hip (inside its namespace):
+// gsr_preprocess_bwd_kernels.inc -- the per-Gaussian backward kernels, included four times by gsr_preprocess_bwd.hip (inside its namespace):
 //   GSR_PBWD_DEPTH 0: preprocess_bwd_kernel, preprocess_bwd_views_kernel, preprocess_bwd_views_waves_kernel (gsr_backward*)
 //   GSR_PBWD_DEPTH 1: preprocess_bwd_depth_kernel, ... _views_depth_kernel, ... _views_waves_depth_kernel (gsr_backward*_depth): one more
 //                     argument -- the blend backward's per-entry dL/dz -- whose per-Gaussian sum joins dL/dtz in the fp64 chain (view_chain).
-// The depth build is a compile-time switch: the GSR_PBWD_DEPTH 0 kernels are the code they were before the depth build existed.
-#if GSR_PBWD_DEPTH
+//   GSR_PBWD_AA 1:    the anti-aliasing builds of both (*_aa_kernel, *_aa_depth_kernel; DESIGN.md section 3f): one more argument -- the
+//                     forward's records, whose staged opacity o' = o c the chain needs -- the o g dc term in view_chain, and every view's
+//                     dL/do' scaled by its own c BEFORE the views are summed.
+// The depth and anti-aliasing builds are compile-time switches: the GSR_PBWD_DEPTH 0 / GSR_PBWD_AA 0 kernels are the code they were before.
+#if GSR_PBWD_DEPTH && GSR_PBWD_AA
+#define GSR_PBWD_NAME(k) k##_aa_depth_kernel
+#elif GSR_PBWD_DEPTH
 #define GSR_PBWD_NAME(k) k##_depth_kernel
+#elif GSR_PBWD_AA
+#define GSR_PBWD_NAME(k) k##_aa_kernel
+#else
+#define GSR_PBWD_NAME(k) k##_kernel
+#endif
+#if GSR_PBWD_DEPTH
 #define GSR_PBWD_DZ_PARAM(...) , __VA_ARGS__
 #define GSR_PBWD_DZ(x) (x)
 #else
-#define GSR_PBWD_NAME(k) k##_kernel
 #define GSR_PBWD_DZ_PARAM(...)
 #define GSR_PBWD_DZ(x) ((const float*)nullptr)
+#endif
+#if GSR_PBWD_AA
+#define GSR_PBWD_AA_PARAM(...) , __VA_ARGS__
+// the trailing view_chain arguments of an anti-aliasing build: the fp32 covariance, the view's staged o' (record part 1, .y), the factor out
+#define GSR_PBWD_AA_ARGS(recs) , cv32, (recs)[GSR_REC_F4 * (size_t)i + 1].y, &caa
+#else
+#define GSR_PBWD_AA_PARAM(...)
+#define GSR_PBWD_AA_ARGS(recs)
 #endif
 
 // ---- single view ------------------------------------------------------------------------------------
@@ -24,7 +42,8 @@ __global__ __launch_bounds__(GSR_BLOCK) void GSR_PBWD_NAME(preprocess_bwd)(
     const float4* __restrict__ partials, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D,
     float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
     float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
-    const uint8_t* __restrict__ used, const uint32_t* __restrict__ tracked, const uint32_t* __restrict__ bwd_error GSR_PBWD_DZ_PARAM(const float* __restrict__ dL_dz)) {
+    const uint8_t* __restrict__ used, const uint32_t* __restrict__ tracked, const uint32_t* __restrict__ bwd_error GSR_PBWD_DZ_PARAM(const float* __restrict__ dL_dz)
+    GSR_PBWD_AA_PARAM(const float4* __restrict__ rec)) {
   const int i = blockIdx.x * GSR_BLOCK + threadIdx.x;
   if (i >= P) return;
   float gm3[3] = {0.f, 0.f, 0.f}, gm2[2] = {0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f;
@@ -47,9 +66,16 @@ __global__ __launch_bounds__(GSR_BLOCK) void GSR_PBWD_NAME(preprocess_bwd)(
     }
     Cov3 cv;
     build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
-    if (GSR_PBWD_DEPTH) view_chain<true>(view, proj, W, H, tanfovx, tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
-                                         reduce_partials_dz(GSR_PBWD_DZ(dL_dz), offsets[i], offsets[i + 1]));
-    else view_chain(view, proj, W, H, tanfovx, tanfovy, p, cv.c, ps, gcov, gm3, gm2);
+#if GSR_PBWD_AA
+    float cv32[6], caa = 1.f;
+    build_cov3_f32(i, mod, scales, rotations, cov3D_precomp, cv32);
+#endif
+    if (GSR_PBWD_DEPTH) view_chain<true, GSR_PBWD_AA>(view, proj, W, H, tanfovx, tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
+                                                      reduce_partials_dz(GSR_PBWD_DZ(dL_dz), offsets[i], offsets[i + 1]) GSR_PBWD_AA_ARGS(rec));
+    else view_chain<false, GSR_PBWD_AA>(view, proj, W, H, tanfovx, tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr, 0.f GSR_PBWD_AA_ARGS(rec));
+#if GSR_PBWD_AA
+    gop = caa * ps.gop;     // dL/do = c dL/do'
+#endif
     if (!cov3D_precomp) cov3_to_scale_rot(cv, mod, gcov, gs, gq);
   }
   if (bwd_error && *bwd_error != 0u) gm3[0] = gm3[1] = gm3[2] = __builtin_nanf("");   // the blend backward of this call aborted: loud, not garbage (GSR_QUEUE_BWD_ERROR)
@@ -73,7 +99,7 @@ __global__ __launch_bounds__(GSR_BLOCK) void GSR_PBWD_NAME(preprocess_bwd_views)
     GsrBwdViews vw, int P, float mod, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, float* __restrict__ dL_dmeans3D,
     float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D GSR_PBWD_DZ_PARAM(GsrDepthViews dz)) {
+    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D GSR_PBWD_DZ_PARAM(GsrDepthViews dz) GSR_PBWD_AA_PARAM(GsrAaViews aa)) {
   const int i = blockIdx.x * GSR_BLOCK + threadIdx.x;
   if (i >= P) return;
   float gm3[3] = {0.f, 0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f;
@@ -81,6 +107,10 @@ __global__ __launch_bounds__(GSR_BLOCK) void GSR_PBWD_NAME(preprocess_bwd_views)
   const float3 p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
   Cov3 cv;
   build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
+#if GSR_PBWD_AA
+  float cv32[6];
+  build_cov3_f32(i, mod, scales, rotations, cov3D_precomp, cv32);
+#endif
   bool any = false;
   for (int v = 0; v < vw.V; ++v) {
     const GsrBwdView& w = vw.v[v];
@@ -91,17 +121,27 @@ __global__ __launch_bounds__(GSR_BLOCK) void GSR_PBWD_NAME(preprocess_bwd_views)
       any = true;
       const PartialSum ps = reduce_partials(w.partials, min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap),
                                             pair || w.dL_dcolors != nullptr || dL_dcolors != nullptr);
+#if GSR_PBWD_AA
+      float caa = 1.f;
+#else
       gop += ps.gop;
+#endif
       if (pair) {   // record layout of the pair backward: geometry sums of both views, then (sum t dx, sum t dy) of this view alone
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a);
+        view_chain<false, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a,
+                                       0.f GSR_PBWD_AA_ARGS(aa.rec[v]));
       } else {
         if (w.dL_dcolors) { w.dL_dcolors[3 * i] = ps.dr; w.dL_dcolors[3 * i + 1] = ps.dg; w.dL_dcolors[3 * i + 2] = ps.db; }
         else { gcol[0] += ps.dr; gcol[1] += ps.dg; gcol[2] += ps.db; }
         if (GSR_PBWD_DEPTH && GSR_PBWD_DZ(dz.dL_dz[v]))   // (a view without a depth gradient: nullptr)
-          view_chain<true>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
-                           reduce_partials_dz(GSR_PBWD_DZ(dz.dL_dz[v]), min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap)));
-        else view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2);
+          view_chain<true, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
+                                        reduce_partials_dz(GSR_PBWD_DZ(dz.dL_dz[v]), min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap))
+                                        GSR_PBWD_AA_ARGS(aa.rec[v]));
+        else view_chain<false, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
+                                            0.f GSR_PBWD_AA_ARGS(aa.rec[v]));
       }
+#if GSR_PBWD_AA
+      gop += caa * ps.gop;    // each view's dL/do' scaled by its own c, then summed
+#endif
     } else if (w.dL_dcolors) {
       w.dL_dcolors[3 * i] = 0.f; w.dL_dcolors[3 * i + 1] = 0.f; w.dL_dcolors[3 * i + 2] = 0.f;
     }
@@ -150,7 +190,7 @@ __global__ __launch_bounds__(64 * MAXW) void GSR_PBWD_NAME(preprocess_bwd_views_
     GsrBwdViews vw, int P, float mod, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, float* __restrict__ dL_dmeans3D,
     float* __restrict__ dL_dcolors, float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D GSR_PBWD_DZ_PARAM(GsrDepthViews dz)) {
+    float* __restrict__ dL_drot, float* __restrict__ dL_dcov3D GSR_PBWD_DZ_PARAM(GsrDepthViews dz) GSR_PBWD_AA_PARAM(GsrAaViews aa)) {
   extern __shared__ float s_part[];                  // [waves][PBW_VALUES + 1][64]  (+1: "this view saw the Gaussian")
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
   const int i = blockIdx.x * 64 + lane;
@@ -162,9 +202,15 @@ __global__ __launch_bounds__(64 * MAXW) void GSR_PBWD_NAME(preprocess_bwd_views_
   const GsrBwdView& w = vw.v[v < 0 ? 0 : v];
   float3 p = make_float3(0.f, 0.f, 0.f);
   Cov3 cv;
+#if GSR_PBWD_AA
+  float cv32[6];
+#endif
   if (live) {
     p = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
     build_cov3(i, mod, scales, rotations, cov3D_precomp, cv);
+#if GSR_PBWD_AA
+    build_cov3_f32(i, mod, scales, rotations, cov3D_precomp, cv32);
+#endif
   }
   float gm3[3] = {0.f, 0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f, gcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float seen = 0.f;
@@ -176,16 +222,25 @@ __global__ __launch_bounds__(64 * MAXW) void GSR_PBWD_NAME(preprocess_bwd_views_
       const PartialSum ps = reduce_partials(w.partials, min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap),
                                             pair || w.dL_dcolors != nullptr || dL_dcolors != nullptr);
       gop = ps.gop;
+#if GSR_PBWD_AA
+      float caa = 1.f;
+#endif
       if (pair) {
-        view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a);
+        view_chain<false, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, ps.dr, ps.dg, gm2a,
+                                       0.f GSR_PBWD_AA_ARGS(aa.rec[v]));
       } else {
         if (w.dL_dcolors) { w.dL_dcolors[3 * i] = ps.dr; w.dL_dcolors[3 * i + 1] = ps.dg; w.dL_dcolors[3 * i + 2] = ps.db; }
         else { gcol[0] = ps.dr; gcol[1] = ps.dg; gcol[2] = ps.db; }
         if (GSR_PBWD_DEPTH && GSR_PBWD_DZ(dz.dL_dz[v]))   // (a view without a depth gradient: nullptr)
-          view_chain<true>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
-                           reduce_partials_dz(GSR_PBWD_DZ(dz.dL_dz[v]), min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap)));
-        else view_chain(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2);
+          view_chain<true, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
+                                        reduce_partials_dz(GSR_PBWD_DZ(dz.dL_dz[v]), min(w.offsets[i], w.cap), min(w.offsets[i + 1], w.cap))
+                                        GSR_PBWD_AA_ARGS(aa.rec[v]));
+        else view_chain<false, GSR_PBWD_AA>(w.view, w.proj, w.W, w.H, w.tanfovx, w.tanfovy, p, cv.c, ps, gcov, gm3, gm2, 0.f, 0.f, nullptr,
+                                            0.f GSR_PBWD_AA_ARGS(aa.rec[v]));
       }
+#if GSR_PBWD_AA
+      gop = caa * ps.gop;     // scaled by this view's c before the LDS exchange sums the views
+#endif
     } else if (w.dL_dcolors) {
       w.dL_dcolors[3 * i] = 0.f; w.dL_dcolors[3 * i + 1] = 0.f; w.dL_dcolors[3 * i + 2] = 0.f;
     }
@@ -243,3 +298,5 @@ __global__ __launch_bounds__(64 * MAXW) void GSR_PBWD_NAME(preprocess_bwd_views_
 #undef GSR_PBWD_NAME
 #undef GSR_PBWD_DZ_PARAM
 #undef GSR_PBWD_DZ
+#undef GSR_PBWD_AA_PARAM
+#undef GSR_PBWD_AA_ARGS

@@ -66,6 +66,9 @@ struct PreOut { uint32_t tiles; uint2 rc; uint32_t tmask; uint32_t depth_bits;
 
 // One Gaussian of one view: cull, project, covariance, conic, radius, rect / alpha box / tile mask, colour; every per-Gaussian output
 // stored.  `i` may be out of range (in_range = false: nothing loaded, nothing stored, an empty result).
+// AA (anti-aliasing): the staged opacity -- and with it the alpha box and the tight lists -- is o * c
+// (gsr_aa_comp); conic, radius, rect, depth and radii are the dilated covariance's either way.
+template <bool AA>
 __device__ __forceinline__ PreOut preprocess_gaussian(
     const GsrPreViews& tab, const GsrPreView& vw, const int i, const int P, float4* __restrict__ s_rec, const bool write_act, int W, int H, int gx, int gy,
     float mod, int sh_degree, int M,
@@ -161,6 +164,7 @@ __device__ __forceinline__ PreOut preprocess_gaussian(
     float a = U00 * T00 + U01 * T01 + U02 * T02;
     float b = U00 * T10 + U01 * T11 + U02 * T12;
     float cc = U10 * T10 + U11 * T11 + U12 * T12;
+    const float a0 = a, c0_ = cc;   // before the dilation (AA)
     a += 0.3f; cc += 0.3f;
     float det = a * cc - b * b;
     if (det != 0.0f) {
@@ -192,7 +196,8 @@ __device__ __forceinline__ PreOut preprocess_gaussian(
         // sqrt(2 ln(255 o) * Sigma_xx), sqrt(.. * Sigma_yy).  The +0.02 on the log (2 % slack on alpha) and the
         // outward rounding make it safe against any fp32 difference with the per-pixel evaluation; pixels
         // outside the box would be skipped by the alpha test anyway, so using it cannot change a result.
-        const float opac = raw ? act_o : opacities[i];
+        const float opac = AA ? (raw ? act_o : opacities[i]) * gsr_aa_comp(gsr_aa_ratio(a0, b, c0_, det))
+                              : (raw ? act_o : opacities[i]);
         const float tau2 = 2.0f * (__logf(255.0f * opac) + 0.02f);
         if (tau2 > 0.0f) {
           const float hx = sqrtf(tau2 * a) + 0.01f, hy = sqrtf(tau2 * cc) + 0.01f;
@@ -301,40 +306,14 @@ __device__ __forceinline__ PreOut preprocess_gaussian(
   return o;
 }
 
-__global__ __launch_bounds__(GSR_BLOCK) void preprocess_fwd_kernel(
-    GsrPreViews tab, int P, int W, int H, int gx, int gy, float mod, int sh_degree, int M,
-    const float* __restrict__ means3D, const float* __restrict__ scales, const float* __restrict__ rotations,
-    const float* __restrict__ opacities, const float* __restrict__ colors_precomp,
-    const float* __restrict__ shs, const float* __restrict__ cov3D_precomp, int tight_lists) {
-  // this block's view (blockIdx.y): its pointers come out of the kernarg table with scalar loads
-  const GsrPreView& vw = tab.v[blockIdx.y];
-  if (vw.skip) return;
-  if (vw.colors) colors_precomp = vw.colors;
-  uint32_t* __restrict__ block_sums = vw.block_sums;
-  __shared__ uint32_t s_wave_sum[GSR_BLOCK / GSR_WAVE];
-  const int i = blockIdx.x * GSR_BLOCK + threadIdx.x;
-  __shared__ float4 s_rec[GSR_BLOCK / GSR_WAVE][256];      // a wave's 64 records on their way to memory (see preprocess_gaussian)
-  const PreOut po = preprocess_gaussian(tab, vw, i, P, s_rec[threadIdx.x >> 6], blockIdx.y == 0, W, H, gx, gy, mod, sh_degree, M, means3D, scales, rotations,
-                                        opacities, colors_precomp, shs, cov3D_precomp, tight_lists);
-  const uint32_t tiles = po.tiles;
-  // Compare mode (single-view entry points, list reuse): is everything the tile lists and the blend decisions depend on bit-equal to an
-  // earlier forward's geometry state?  One word per block for the host (it rides in the copy that brings the entry counts): 0 = equal.
-  // (Rounds 3 - 4 compared a 64-bit fingerprint instead -- "identical up to a 2^-64 coincidence"; the bar for integer work is bit-exact.)
-  const int any = vw.block_hash ? __syncthreads_or(po.differs ? 1 : 0) : 0;
-  // per-block total of tiles_touched: feeds the two-level offsets scan (no full-length scan kernel)
-  uint32_t wsum = tiles;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) wsum += __shfl_xor(wsum, m, 64);
-  if ((threadIdx.x & 63) == 0) s_wave_sum[threadIdx.x >> 6] = wsum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t total = s_wave_sum[0] + s_wave_sum[1] + s_wave_sum[2] + s_wave_sum[3];
-    block_sums[blockIdx.x] = total;
-    // the verdict word and the block's entry count in one 8-byte store: block_hash may be PINNED HOST memory (gsr_forward_capacity), where
-    // the host adds the counts up as soon as this kernel's blocks are through (gsr_wait_block_counts) -- no readback, no later kernel
-    if (vw.block_hash) vw.block_hash[blockIdx.x] = make_uint2(any ? 1u : 0u, total);
-  }
-}
+// The preprocess kernel is written once (gsr_preprocess_fwd_kernel.inc) and compiled twice: GSR_PFWD_AA 0 gives preprocess_fwd_kernel,
+// 1 its anti-aliasing build preprocess_fwd_aa_kernel (same arguments).
+#define GSR_PFWD_AA 0
+#include "gsr_preprocess_fwd_kernel.inc"
+#undef GSR_PFWD_AA
+#define GSR_PFWD_AA 1
+#include "gsr_preprocess_fwd_kernel.inc"
+#undef GSR_PFWD_AA
 
 __global__ __launch_bounds__(GSR_BLOCK) void mark_visible_kernel(int P, const float* __restrict__ view,
                                                                  const float* __restrict__ means3D,
@@ -356,9 +335,13 @@ int gsr_launch_preprocess(const GsrPreViews& tab, const GsrCam& cam, int P, cons
   const char* ref_lists = getenv("GSR_REFERENCE_LISTS");
   const int tight = (ref_lists && ref_lists[0] == '1') ? 0 : 1;
   { GSR_PROF("preprocess_fwd", st);
-  hipLaunchKernelGGL(preprocess_fwd_kernel, dim3(blocks, tab.V), dim3(GSR_BLOCK), 0, st, tab, P, cam.W, cam.H, cam.gx,
-                     cam.gy, cam.scale_modifier, cam.sh_degree, cam.M, means3D, scales, rotations, opacities,
-                     colors_precomp, shs, cov3D_precomp, tight); }
+#define PFWD_LAUNCH(K) hipLaunchKernelGGL(K, dim3(blocks, tab.V), dim3(GSR_BLOCK), 0, st, tab, P, cam.W, cam.H, cam.gx, cam.gy,             \
+                                          cam.scale_modifier, cam.sh_degree, cam.M, means3D, scales, rotations, opacities, colors_precomp, \
+                                          shs, cov3D_precomp, tight)
+  if (cam.antialiasing) PFWD_LAUNCH(preprocess_fwd_aa_kernel);
+  else PFWD_LAUNCH(preprocess_fwd_kernel);
+#undef PFWD_LAUNCH
+  }
   GSR_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -52,14 +52,14 @@ struct Settings {
 
 Settings make_settings(const torch::Tensor& bg, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& campos,
                        double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, int64_t M, bool prefiltered,
-                       const c10::Device& dev) {
+                       const c10::Device& dev, bool antialiasing = false) {
   Settings o;
   o.bg = f32c(bg, dev); o.view = f32c(viewmatrix, dev); o.proj = f32c(projmatrix, dev); o.campos = f32c(campos, dev);
   TORCH_CHECK(o.bg.numel() >= 3 && o.view.numel() >= 16 && o.proj.numel() >= 16 && o.campos.numel() >= 3,
               "raster settings: bg / campos must hold 3 floats, viewmatrix / projmatrix 16");
   o.s.image_height = (int32_t)H; o.s.image_width = (int32_t)W;
   o.s.tanfovx = (float)tanfovx; o.s.tanfovy = (float)tanfovy; o.s.scale_modifier = (float)scale_modifier;
-  o.s.sh_degree = (int32_t)degree; o.s.sh_coeffs = (int32_t)M; o.s.prefiltered = prefiltered ? 1 : 0;
+  o.s.sh_degree = (int32_t)degree; o.s.sh_coeffs = (int32_t)M; o.s.prefiltered = (prefiltered ? 1 : 0) | (antialiasing ? GSR_SETTINGS_ANTIALIASING : 0);
   o.s.bg = o.bg.data_ptr<float>(); o.s.viewmatrix = o.view.data_ptr<float>(); o.s.projmatrix = o.proj.data_ptr<float>();
   o.s.campos = o.campos.data_ptr<float>();
   return o;
@@ -81,6 +81,7 @@ struct ListCache {
   uint32_t D = 0;           // entries of the cached forward
   uint32_t layout = 0;      // the num_rendered its binning state was laid out for (= D, or the capacity of a capacity-mode forward)
   void* stream = nullptr;   // the stream the lists were produced on: a forward on ANOTHER stream is not ordered behind their writes -- it bins its own
+  bool antialiasing = false;   // the lists of an anti-aliased forward (shorter: o c < o) are never handed to a plain one, nor the reverse
   torch::Tensor geom, binning, image;
 };
 
@@ -101,7 +102,7 @@ struct ListCache {
 constexpr int64_t kCompareMaxP = 2048 * 256;     // the library compares up to this many Gaussians (GSR_HOST_SCAN_MAX_BLOCKS blocks)
 struct LayerState {
   ListCache lists;                                              // the last forward's states (tile-list reuse)
-  std::map<std::tuple<int64_t, int64_t, int64_t>, uint32_t> cap;   // remembered entry capacity per (P, H, W)
+  std::map<std::tuple<int64_t, int64_t, int64_t, bool>, uint32_t> cap;   // remembered entry capacity per (P, H, W, anti-aliasing)
   int32_t* pinned = nullptr;   // COHERENT pinned host words: [0] the tile-order kernel's count (P > 512 Ki), [2 ...] the preprocess blocks' {differs, entry count} pairs
   bool twin[2] = {false, false};   // was the last forward / the one before it a twin of its predecessor
   bool capacity = true;        // switch: capacity-mode forwards
@@ -128,7 +129,8 @@ Forward rasterize_forward(const torch::Tensor& background, const torch::Tensor& 
                           int64_t image_width, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos, bool prefiltered,
                           bool will_backward,       // false = no input requires a gradient -- the blend records nothing for a backward
                           bool allow_capacity,      // false = the caller hands num_rendered on (upstream's tuple): layout must equal the count
-                          LayerState* S) {          // what the layer may remember and reuse; nullptr = nothing (a pure function, as upstream's)
+                          LayerState* S,            // what the layer may remember and reuse; nullptr = nothing (a pure function, as upstream's)
+                          bool antialiasing) {      // GSR_SETTINGS_ANTIALIASING
   TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
   TORCH_CHECK(means3D.is_cuda(), "diff_gaussian_rasterization (MI355X build) runs on a HIP device only; there is no CPU fallback");
   const c10::Device dev = means3D.device();
@@ -146,7 +148,8 @@ Forward rasterize_forward(const torch::Tensor& background, const torch::Tensor& 
   check_counts("rasterize_gaussians", P, colors, opacity, scales, rotations, cov3D_precomp, sh);
   const torch::Tensor m3 = f32c(means3D, dev), col = f32c(colors, dev), op = f32c(opacity, dev), sc = f32c(scales, dev),
                       rot = f32c(rotations, dev), cov = f32c(cov3D_precomp, dev), shs = f32c(sh, dev);
-  Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, prefiltered, dev);
+  Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, prefiltered, dev,
+                              antialiasing);
   torch::Tensor color = torch::empty({3, H, W}, f32), depth = torch::empty({1, H, W}, f32);
   torch::Tensor radii = torch::empty({P}, f32.dtype(torch::kInt32));
   torch::Tensor geom = torch::empty({(int64_t)gsr_geom_bytes((int32_t)P)}, u8);
@@ -165,7 +168,7 @@ Forward rasterize_forward(const torch::Tensor& background, const torch::Tensor& 
   ListCache& lc = S ? S->lists : none;
   const bool reuse = S && S->reuse;
   const bool candidate = reuse && lc.valid && lc.dev == dev.index() && lc.P == P && lc.H == H && lc.W == W && lc.stream == stream &&
-                         (allow_capacity || lc.layout == lc.D);
+                         lc.antialiasing == antialiasing && (allow_capacity || lc.layout == lc.D);
   const uint32_t fwd_flags = will_backward ? 0u : (uint32_t)GSR_FORWARD_ONLY;
   auto finish = [&](uint32_t count, uint32_t layout, const torch::Tensor& binning) {
     Forward o;
@@ -176,12 +179,13 @@ Forward rasterize_forward(const torch::Tensor& background, const torch::Tensor& 
     if (!S) return;
     if (reuse && count > 0) {
       lc.valid = true; lc.dev = dev.index(); lc.P = P; lc.H = H; lc.W = W; lc.D = count; lc.layout = layout; lc.stream = stream;
+      lc.antialiasing = antialiasing;
       lc.geom = geom; lc.binning = binning; lc.image = image;
     } else {
       lc = ListCache();
     }
   };
-  const auto key = std::make_tuple(P, H, W);
+  const auto key = std::make_tuple(P, H, W, antialiasing);
   if (S && allow_capacity && S->capacity && S->cap.count(key) && !(candidate && S->twin[1])) {
     LayerState& cs = *S;
     const auto known = cs.cap.find(key);
@@ -253,9 +257,11 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, double tan_fovx, double tan_fovy, int64_t image_height,
                     int64_t image_width, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos, bool prefiltered,
                     bool will_backward,       // extension over upstream (default true)
-                    const std::shared_ptr<LayerState>& state) {   // extension (default none): tile-list reuse across calls (exact mode either way)
+                    const std::shared_ptr<LayerState>& state,   // extension (default none): tile-list reuse across calls (exact mode either way)
+                    bool antialiasing) {      // extension (default false): GSR_SETTINGS_ANTIALIASING; give the backward the same
   Forward o = rasterize_forward(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
-                                tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, will_backward, false, state.get());
+                                tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, will_backward, false, state.get(),
+                                antialiasing);
   return std::make_tuple(o.D, o.color, o.depth, o.radii, o.geom, o.binning, o.image);
 }
 
@@ -271,7 +277,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
                              const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                              bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
                              const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W], the depth build
-                             const c10::optional<torch::Tensor>& dL_dout_alpha) {  // extension (default None): [1, H, W], the alpha term
+                             const c10::optional<torch::Tensor>& dL_dout_alpha,    // extension (default None): [1, H, W], the alpha term
+                             bool antialiasing) {  // extension (default false): the forward's GSR_SETTINGS_ANTIALIASING
   const c10::Device dev = means3D.device();
   c10::hip::HIPGuard guard(dev.index());
   const int64_t P = means3D.size(0);
@@ -300,7 +307,8 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   }
   const torch::Tensor m3 = f32c(means3D, dev), col = f32c(colors, dev), sc = f32c(scales, dev), rot = f32c(rotations, dev),
                       cov = f32c(cov3D_precomp, dev), shs = f32c(sh, dev), g = f32c(dL_dout_color, dev);
-  Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev);
+  Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev,
+                              antialiasing);
   void* stream = (void*)c10::hip::getCurrentHIPStream(dev.index()).stream();
   auto optr = [](torch::Tensor& t) -> float* { return t.numel() ? t.data_ptr<float>() : nullptr; };
   // the depth image's gradient (the depth build, its larger scratch) and the rendered alpha's: NULL when absent, both NULL is gsr_backward
@@ -334,13 +342,14 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                                 torch::Tensor rotations, torch::Tensor cov3D, torch::Tensor bg, torch::Tensor viewmatrix,
                                                 torch::Tensor projmatrix, torch::Tensor campos, double tanfovx, double tanfovy, int64_t H,
                                                 int64_t W, double scale_modifier, int64_t degree, bool prefiltered, bool will_backward,
-                                                bool differentiable_depth, bool return_alpha) {
+                                                bool differentiable_depth, bool return_alpha, bool antialiasing) {
     (void)means2D;
     // grad_depth is ignored unless differentiable_depth, an unused alpha has no gradient: do not let autograd fill zero images for them
     ctx->set_materialize_grads(false);
     ctx->saved_data["depth"] = differentiable_depth;
+    ctx->saved_data["antialiasing"] = antialiasing;   // the backward differentiates THIS forward: the flag is not asked for again
     Forward r = rasterize_forward(bg, means3D, colors, opacities, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tanfovx,
-                                  tanfovy, H, W, sh, degree, campos, prefiltered, will_backward, true, t_call_state);
+                                  tanfovy, H, W, sh, degree, campos, prefiltered, will_backward, true, t_call_state, antialiasing);
     torch::Tensor color = r.color, depth = r.depth, radii = r.radii;
     torch::Tensor alpha;
     if (return_alpha) {      // 1 - final_T of this call's own image state (P = 0: nothing blended, alpha 0)
@@ -364,7 +373,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     return {color, radii, depth};
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    torch::autograd::variable_list out(22);       // one slot per forward argument; undefined = no gradient
+    torch::autograd::variable_list out(23);       // one slot per forward argument; undefined = no gradient
     if (ctx->saved_data["empty"].toBool()) return out;
     const auto sv = ctx->get_saved_variables();
     const torch::Tensor &m3 = sv[0], &radii = sv[1], &col = sv[2], &sh = sv[3], &sc = sv[4], &rot = sv[5], &cov = sv[6], &geom = sv[7],
@@ -383,7 +392,8 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     const bool want_col = has_col && ctx->needs_input_grad(3);      // frozen colours (the reference's training): the six-sum backward
     auto r = rasterize_gaussians_backward(bg, m3, radii, col, sc, rot, ctx->saved_data["scale_modifier"].toDouble(), cov, view, proj,
                                           ctx->saved_data["tanfovx"].toDouble(), ctx->saved_data["tanfovy"].toDouble(), g, sh,
-                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd, ga);
+                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd, ga,
+                                          ctx->saved_data["antialiasing"].toBool());
     out[0] = std::get<3>(r);                      // means3D
     out[1] = std::get<0>(r);                      // means2D (x, y in NDC units, z = 0)
     if (has_sh) out[2] = std::get<5>(r);
@@ -406,7 +416,8 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
           const torch::Tensor& bg, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const torch::Tensor& campos,
           double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered,
           bool differentiable_depth,     // extension: the depth output is differentiated too (the depth build)
-          bool return_alpha) {           // extension: a fourth output, the rendered alpha 1 - final_T (differentiable)
+          bool return_alpha,             // extension: a fourth output, the rendered alpha 1 - final_T (differentiable)
+          bool antialiasing) {           // extension: the opacity compensation (GSR_SETTINGS_ANTIALIASING)
   bool will_backward = false;
   if (at::GradMode::is_enabled())
     for (const torch::Tensor* t : {&means3D, &means2D, &sh, &colors, &opacities, &scales, &rotations, &cov3D})
@@ -417,7 +428,7 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
     ~Scope() { t_call_state = prev; }
   } scope(state.get());
   auto o = RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos, tanfovx,
-                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth, return_alpha);
+                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth, return_alpha, antialiasing);
   if (return_alpha) return pybind11::make_tuple(o[0], o[1], o[2], o[3]);
   return pybind11::make_tuple(o[0], o[1], o[2]);
 }
@@ -457,21 +468,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         d["capacities"] = (int64_t)s.cap.size(); d["twin_history"] = py::make_tuple(s.twin[0], s.twin[1]);
         return d;
       });
-  // upstream's 18 arguments, then the two extensions (will_backward, state)
+  // upstream's 18 arguments, then the extensions (will_backward, state, antialiasing)
   m.def("rasterize_gaussians", &rasterize_gaussians, py::arg("background"), py::arg("means3D"), py::arg("colors"), py::arg("opacity"),
         py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"),
         py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("image_height"), py::arg("image_width"), py::arg("sh"), py::arg("degree"),
-        py::arg("campos"), py::arg("prefiltered"), py::arg("will_backward") = true, py::arg("state") = std::shared_ptr<LayerState>());
+        py::arg("campos"), py::arg("prefiltered"), py::arg("will_backward") = true, py::arg("state") = std::shared_ptr<LayerState>(),
+        py::arg("antialiasing") = false);
   m.def("rasterize_gaussians_backward", &rasterize_gaussians_backward, py::arg("background"), py::arg("means3D"), py::arg("radii"),
         py::arg("colors"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"),
         py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color"), py::arg("sh"),
         py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"), py::arg("binningBuffer"), py::arg("imageBuffer"),
-        py::arg("want_color_grad") = true, py::arg("dL_dout_depth") = py::none(), py::arg("dL_dout_alpha") = py::none());
+        py::arg("want_color_grad") = true, py::arg("dL_dout_depth") = py::none(), py::arg("dL_dout_alpha") = py::none(),
+        py::arg("antialiasing") = false);
   // one GaussianRasterizer call: forward + the autograd node (C++); first argument: the LayerState or None
   m.def("rasterize", &rasterize, py::arg("state"), py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"), py::arg("opacities"),
         py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"),
         py::arg("tanfovx"), py::arg("tanfovy"), py::arg("H"), py::arg("W"), py::arg("scale_modifier"), py::arg("degree"), py::arg("prefiltered"),
-        py::arg("differentiable_depth") = false, py::arg("return_alpha") = false);
+        py::arg("differentiable_depth") = false, py::arg("return_alpha") = false, py::arg("antialiasing") = false);
   m.def("mark_visible", &mark_visible);
   m.def("abi_version", []() { return (int)GSR_VERSION; });   // the header this layer was COMPILED against (compare with the library's gsr_version())
 }

@@ -107,7 +107,7 @@ def _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales,
     """One gradient slot per apply() argument: None for the inputs the call did not have and for the settings and the two switches."""
     has_sh, has_col, has_sc, has_cov = ctx.has
     return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity, d_scales if has_sc else None,
-            d_rot if has_sc else None, d_cov if has_cov else None, None, None, None)
+            d_rot if has_sc else None, d_cov if has_cov else None, None, None, None, None)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -116,7 +116,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, differentiable_depth=False, return_alpha=False):
+                raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False):
         # grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it (or for an unused colour / alpha)
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
@@ -136,7 +136,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.empty = False
         sh_, col_, op_ = _prep(sh), _prep(colors_precomp), _prep(opacities)
         sc_, rot_, cov_ = _prep(scales), _prep(rotations), _prep(cov3Ds_precomp)
-        color, radii, depth, state = _hip.rasterize_forward(raster_settings, m3, op_, col_, sh_, sc_, rot_, cov_)
+        # (the state's settings carry the anti-aliasing bit: the backward takes it from there)
+        color, radii, depth, state = _hip.rasterize_forward(raster_settings, m3, op_, col_, sh_, sc_, rot_, cov_,
+                                                            **({"antialiasing": True} if antialiasing else {}))
         ctx.state = state
         _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_)
         if ctx.alpha:
@@ -147,7 +149,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
         # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth; grad_alpha: used whenever autograd delivers one
         if ctx.empty:
-            return (None,) * 11
+            return (None,) * 12
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         if grad_color is None:
@@ -169,7 +171,7 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
-                differentiable_depth=False, return_alpha=False):
+                differentiable_depth=False, return_alpha=False, antialiasing=False):
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
         ctx.alpha = bool(return_alpha)
@@ -181,7 +183,8 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         wants_grad = any(ctx.needs_input_grad)
         color, radii, depth, states = _hip.rasterize_forward_batch(list(settings_list), m3, op_, col_, sh_, sc_, rot_, cov_,
                                                                    prepare_backward=wants_grad, **({} if wants_grad else {"forward_only": True}),
-                                                                   **({"depth_scratch": True} if (ctx.depth and wants_grad) else {}))
+                                                                   **({"depth_scratch": True} if (ctx.depth and wants_grad) else {}),
+                                                                   **({"antialiasing": True} if antialiasing else {}))
         ctx.states = states
         _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_)
         if ctx.alpha:
@@ -207,13 +210,14 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False):
+                              rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False, antialiasing=False):
     """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder.
     ``differentiable_depth``: the depth output [V,1,H,W] is differentiated too (see GaussianRasterizer); views that share a camera,
     which the backward otherwise fuses into one pass, are then differentiated unfused.
     ``return_alpha``: a fourth output, the rendered alpha [V,1,H,W] = 1 - final_T, always differentiable (see GaussianRasterizer); views
     that share a camera stay fused.  A view's ``means2D`` gradient then includes its own alpha term: a caller that wants a colour-only
-    densification statistic must render alpha with a separate call (its own means2D holder)."""
+    densification statistic must render alpha with a separate call (its own means2D holder).
+    ``antialiasing``: every view is rendered with the opacity compensation (see GaussianRasterizer)."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -232,7 +236,8 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
             means3D, means2D if whole else means2D[lo:hi], empty if shs is None else shs,
             empty if colors_precomp is None else (colors_precomp[lo:hi] if (per_view_col and not whole) else colors_precomp), opacities,
             empty if scales is None else scales, empty if rotations is None else rotations,
-            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth), bool(return_alpha))
+            empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth), bool(return_alpha),
+            bool(antialiasing))
     if V <= _hip.MAX_BATCH:
         return call(0, V)
     # more views than one library call takes: several calls, outputs concatenated (autograd sums the shared inputs)
@@ -241,8 +246,9 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, differentiable_depth=False, return_alpha=False):
-    """One view (upstream's entry point).  ``return_alpha``: a fourth output, the rendered alpha [1,H,W] (see GaussianRasterizer)."""
+                        raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False):
+    """One view (upstream's entry point).  ``return_alpha``: a fourth output, the rendered alpha [1,H,W] (see GaussianRasterizer).
+    ``antialiasing``: the opacity compensation (see GaussianRasterizer)."""
     native = _native() if (means3D is not None and means3D.is_cuda) else None
     if native is not None and not _PY_NODE:
         # one crossing into the torch C++ layer: forward and the autograd node live there (csrc/gsr_torch.cpp: RasterizeFn)
@@ -250,9 +256,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         return native.rasterize(layer_state(means3D.device), means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, rs.bg, rs.viewmatrix,
                                 rs.projmatrix, rs.campos, float(rs.tanfovx), float(rs.tanfovy), int(rs.image_height), int(rs.image_width),
                                 float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered),
-                                differentiable_depth=bool(differentiable_depth), return_alpha=bool(return_alpha))
+                                differentiable_depth=bool(differentiable_depth), return_alpha=bool(return_alpha),
+                                antialiasing=bool(antialiasing))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha))
+                                     cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha), bool(antialiasing))
 
 
 class GaussianRasterizer(nn.Module):
@@ -268,13 +275,22 @@ class GaussianRasterizer(nn.Module):
     colours = 1 on black.  It is always differentiable: its gradient reaches means2D, opacities, the covariance (scales / rotations or
     cov3D_precomp) and means3D, never the colours or SHs.  ``means2D.grad`` then includes the alpha term, as autograd requires: a caller
     that wants a colour-only densification statistic must render alpha with a separate call (its own means2D holder).  False: upstream's
-    three outputs."""
+    three outputs.
 
-    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False, return_alpha: bool = False):
+    ``antialiasing`` (extension, default False; upstream's ``antialiasing`` rasterizer setting, Mip-Splatting's 2D filter): each Gaussian's
+    opacity is scaled by c = sqrt(max(det0 / det1, 2.5e-5)), det0 / det1 the determinants of its screen-space covariance before / after
+    the fixed 0.3 px^2 dilation, so a Gaussian smaller than a pixel keeps the energy of its undilated footprint instead of being drawn too
+    fat and too bright.  The opacity gradient is dL/do = c dL/d(o c), and the term through c reaches the covariance (scales / rotations or
+    cov3D_precomp) and means3D.  Conic, radii, depth and the tile rects are unchanged.  Combines with ``differentiable_depth`` and
+    ``return_alpha``.  False: every output and gradient is bit for bit the plain render's.  """
+
+    def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False, return_alpha: bool = False,
+                 antialiasing: bool = False):
         super().__init__()
         self.raster_settings = raster_settings
         self.differentiable_depth = bool(differentiable_depth)
         self.return_alpha = bool(return_alpha)
+        self.antialiasing = bool(antialiasing)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -298,4 +314,5 @@ class GaussianRasterizer(nn.Module):
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha)
+                                   cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha,
+                                   antialiasing=self.antialiasing)

@@ -313,14 +313,18 @@ class RasterState:
         self.raw_fused = None    # (unnorm_rotations,) when the activations ran inside the forward: the backward applies their chain too
 
 
-def _make_settings(rs, dev, sh_coeffs: int):
+ANTIALIASING = 2        # GSR_SETTINGS_ANTIALIASING of include/gsr.h: bit 1 of gsr_settings.prefiltered
+
+
+def _make_settings(rs, dev, sh_coeffs: int, antialiasing: bool = False):
     keep = (_dev_f32(rs.bg, dev, 3, "bg"), _dev_f32(rs.viewmatrix, dev, 16, "viewmatrix"),
             _dev_f32(rs.projmatrix, dev, 16, "projmatrix"), _dev_f32(rs.campos, dev, 3, "campos"))
     s = GsrSettings()
     s.image_height, s.image_width = int(rs.image_height), int(rs.image_width)
     s.tanfovx, s.tanfovy = float(rs.tanfovx), float(rs.tanfovy)
     s.scale_modifier = float(rs.scale_modifier)
-    s.sh_degree, s.sh_coeffs, s.prefiltered = int(rs.sh_degree), int(sh_coeffs), int(bool(rs.prefiltered))
+    s.sh_degree, s.sh_coeffs = int(rs.sh_degree), int(sh_coeffs)
+    s.prefiltered = int(bool(rs.prefiltered)) | (ANTIALIASING if antialiasing else 0)
     s.bg, s.viewmatrix, s.projmatrix, s.campos = (k.data_ptr() for k in keep)
     return s, keep
 
@@ -332,9 +336,10 @@ def _require_device(t: torch.Tensor):
             f"'{t.device}'. There is no CPU fallback.")
 
 
-def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotations, cov3D_precomp
+def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotations, cov3D_precomp, antialiasing: bool = False
                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, RasterState]:
-    """K1..K6.  Returns (color[3,H,W], radii[P] int32, depth[1,H,W], state)."""
+    """K1..K6.  Returns (color[3,H,W], radii[P] int32, depth[1,H,W], state).  ``antialiasing``: GSR_SETTINGS_ANTIALIASING (DESIGN.md
+    section 3f); the state's settings keep the bit, so its backward differentiates the same forward."""
     lib = load_library()
     _require_device(means3D)
     dev = means3D.device
@@ -342,7 +347,7 @@ def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotat
     H, W = int(rs.image_height), int(rs.image_width)
     M = 0 if shs is None else int(shs.shape[1])
     with _on(dev):
-        s, keep = _make_settings(rs, dev, M)
+        s, keep = _make_settings(rs, dev, M, antialiasing)
         u8 = dict(dtype=torch.uint8, device=dev)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
@@ -447,12 +452,13 @@ FORWARD_ONLY = 1        # GSR_FORWARD_ONLY of include/gsr.h
 
 def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, shs, scales, rotations, cov3D_precomp,
                             prepare_backward: bool = False, no_host_sync: bool = False, raw=None, forward_only: bool = False,
-                            grad_out=None, depth_cuts=None, depth_scratch: bool = False):
+                            grad_out=None, depth_cuts=None, depth_scratch: bool = False, antialiasing: bool = False):
     """All views of a step in one call: one launch per stage for all views, one host sync for all duplicate counts.  Returns (color[V,3,H,W], radii[V,P] int32, depth[V,1,H,W], states[V]).
     ``depth_cuts = (cut_in, cut_out, redo[, margin = 1.01])`` (forward_only calls; include/gsr.h: gsr_arm_depth_cuts): per view a [T] int32 tensor of depth
     bits to bin with (or None), a [T] int32 tensor that receives the next frame's proposal, and one zeroed [V] int32 tensor of redo flags.
     ``depth_scratch``: the backward that follows will take a depth gradient -- the pre-allocated scratch is sized for it
     (gsr_backward_scratch_bytes_depth).
+    ``antialiasing``: GSR_SETTINGS_ANTIALIASING for every view; the states keep it for the backward.
     ``raw = (unnorm_rotations, logit_opacities, log_scales)`` (then ``opacities`` / ``scales`` / ``rotations`` are None): the
     activations are applied inside the preprocess kernel when the call runs in capacity mode (``states[0].raw_fused``), by
     ``activate_forward`` otherwise; either way ``states[0].act = (rotations, opacities, scales)`` holds the activated tensors."""
@@ -480,14 +486,14 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
         # SH colours depend on the camera position, and the multi-view backward kernel covers precomputed colours only: every
         # view takes the single-view entry points, so that each state owns the tile order / queue / binning that
         # gsr_backward reads (the batch state of a multi-view call keeps them in one shared table instead).
-        outs = [rasterize_forward(rs, means3D, opacities, None, shs, scales, rotations, cov3D_precomp) for rs in settings_list]
+        outs = [rasterize_forward(rs, means3D, opacities, None, shs, scales, rotations, cov3D_precomp, antialiasing) for rs in settings_list]
         return (torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs]), torch.stack([o[2] for o in outs]),
                 [o[3] for o in outs])
     with _on(dev):
         sarr = (GsrSettings * V)()
         keeps = []
         for v, rs in enumerate(settings_list):
-            s, keep = _make_settings(rs, dev, M)
+            s, keep = _make_settings(rs, dev, M, antialiasing)
             sarr[v] = s
             keeps.append(keep)
         u8 = dict(dtype=torch.uint8, device=dev)

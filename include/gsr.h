@@ -45,12 +45,21 @@ typedef struct gsr_settings {
   float scale_modifier;
   int32_t sh_degree;   /* active SH degree (0..3) */
   int32_t sh_coeffs;   /* M: coefficients per Gaussian in `shs` ([P,M,3]); 0 when colors_precomp is used */
-  int32_t prefiltered; /* accepted for API parity; reference call sites always pass False */
+  int32_t prefiltered; /* bit 0: accepted for API parity (reference call sites always pass False); bit 1: GSR_SETTINGS_ANTIALIASING.
+                          Other bits are rejected (-2). */
   const float* bg;         /* [3]  device */
   const float* viewmatrix; /* [16] device */
   const float* projmatrix; /* [16] device */
   const float* campos;     /* [3]  device */
 } gsr_settings;
+/* Anti-aliasing (opt-in), carried in bit 1 of gsr_settings.prefiltered: the preprocess scales each Gaussian's
+ * activated opacity by c = sqrt(max(det0 / det1, 2.5e-5)), det0 = A C - B^2 of the projected 2D covariance before the 0.3 px^2 dilation,
+ * det1 the dilated determinant the conic uses (Mip-Splatting's 2D filter, upstream's `antialiasing` setting).  The staged opacity o c is
+ * what the blend, the alpha box and the tight tile lists use; conic, radius, rect, depth and radii are unchanged.  The backward entry
+ * points take the bit from their own settings and must be given the forward's: dL_dopacity is then dL/do = c dL/d(o c) per view, and
+ * the term o dL/d(o c) dc reaches dL_dmeans3D, dL_dscales, dL_drotations and dL_dcov3D.  In a batch call every view's settings must
+ * agree on the bit (-2 otherwise).  Without the bit every output and gradient is the plain path's, bit for bit. */
+#define GSR_SETTINGS_ANTIALIASING 2
 
 /* ---- buffer sizes (bytes).  The three opaque state buffers play the role of the reference
  * extension's geomBuffer / binningBuffer / imgBuffer, but are sized by the caller up front. */
