@@ -503,19 +503,47 @@ int gsr_forward_render_shared_ex(const gsr_settings* s, int32_t P, uint32_t num_
 }
 
 }  // extern "C"
-// gsr_backward, gsr_backward_depth and gsr_backward_ext: dL_ddepth == dL_dalpha == nullptr is exactly gsr_backward
+// The camera pass's table (gsr_backward_cam / gsr_backward_batch_cam)
+static void camera_header(GsrCamViews& cv, int V, int32_t P, const GsrCam& cam, const uint32_t* bwd_error, const float* means3D,
+                          const float* scales, const float* rotations, const float* cov3D_precomp, const float* shs) {
+  cv.V = V; cv.P = P; cv.nblk = gsr_camera_blocks(P, cam.H, cam.W); cv.sh_degree = cam.sh_degree; cv.M = cam.M;
+  cv.mod = cam.scale_modifier; cv.bwd_error = bwd_error;
+  cv.means3D = means3D; cv.scales = scales; cv.rotations = rotations; cv.cov3D = cov3D_precomp; cv.shs = shs;
+}
+static void camera_view(GsrCamView& w, const GsrCam& cam, const gsr_camera_grads& cg, double* slab, const int32_t* radii, const GeomState* g,
+                        const float4* partials, const float* dL_dz, const float* final_T, const uint32_t* clamped, uint32_t cap,
+                        const float* dL_dcolor) {
+  w.view = cam.view; w.proj = cam.proj; w.campos = cam.campos;
+  w.radii = radii; w.used = g ? g->used : nullptr; w.tracked = g ? g->counters + 1 : nullptr; w.offsets = g ? g->offsets : nullptr;
+  w.partials = partials; w.dL_dz = dL_dz; w.rec = g ? g->rec : nullptr; w.clamped = clamped;
+  w.final_T = final_T; w.dL_dcolor = cg.dL_dbg ? dL_dcolor : nullptr; w.slab = slab;
+  w.out_view = cg.dL_dviewmatrix; w.out_proj = cg.dL_dprojmatrix; w.out_campos = cg.dL_dcampos; w.out_bg = cg.dL_dbg;
+  w.cap = cap; w.W = cam.W; w.H = cam.H; w.tanfovx = cam.tanfovx; w.tanfovy = cam.tanfovy;
+}
+extern "C" size_t gsr_camera_scratch_bytes(int32_t V, int32_t P, int32_t H, int32_t W) {
+  return gsr_align((size_t)(V > 0 ? V : 1) * (size_t)gsr_camera_blocks(P, H, W) * GSR_CAM_ROW * sizeof(double));
+}
+
+// gsr_backward, gsr_backward_depth, gsr_backward_ext and gsr_backward_cam: dL_ddepth == dL_dalpha == cg == nullptr is exactly gsr_backward
 static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                         const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
                         const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
                         const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                         float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                        const float* dL_dalpha, void* stream) {
-  GsrRange _range(dL_ddepth ? "gsr_backward_depth" : (dL_dalpha ? "gsr_backward_alpha" : "gsr_backward"));
+                        const float* dL_dalpha, void* stream, const gsr_camera_grads* cg = nullptr, void* cam_scratch = nullptr) {
+  GsrRange _range(cg ? "gsr_backward_cam" : (dL_ddepth ? "gsr_backward_depth" : (dL_dalpha ? "gsr_backward_alpha" : "gsr_backward")));
   GsrCam cam;
   if (int rc = make_cam(s, &cam)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (P <= 0) return 0;
+  if (cg && (!cam_scratch || !dL_dcolor)) { gsr_set_error("gsr_backward_cam: NULL cam_scratch / dL_dcolor"); return -2; }
+  if (P <= 0) {   // nothing blended: the image is the background (T = 1 everywhere), every other camera gradient is 0
+    if (!cg) return 0;
+    GsrCamViews cv;
+    camera_header(cv, 1, 0, cam, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    camera_view(cv.v[0], cam, *cg, (double*)cam_scratch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dL_dcolor);
+    return gsr_launch_camera_bwd(cv, false, st);
+  }
   if (!means3D || !radii || !geom_state || !image_state || !dL_dcolor || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity) {
     gsr_set_error("gsr_backward: NULL argument");
     return -2;
@@ -539,9 +567,16 @@ static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered,
     if (dL_dz) { dv.dL_ddepth[0] = dL_ddepth; dv.dL_dz[0] = dL_dz; }
     if (int rc = gsr_launch_render_bwd(rt, st, dL_dz ? &dv : nullptr)) return rc;
   }
-  return gsr_launch_preprocess_bwd(cam, P, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, g,
-                                   partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales,
-                                   dL_drotations, dL_dcov3D, dL_dsh, num_rendered > 0 ? im.queue + GSR_QUEUE_BWD_ERROR : nullptr, st, dL_dz);
+  const uint32_t* bwd_error = num_rendered > 0 ? im.queue + GSR_QUEUE_BWD_ERROR : nullptr;
+  if (int rc = gsr_launch_preprocess_bwd(cam, P, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, g,
+                                         partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales,
+                                         dL_drotations, dL_dcov3D, dL_dsh, bwd_error, st, dL_dz))
+    return rc;
+  if (!cg) return 0;
+  GsrCamViews cv;   // the camera pass: the same records, behind the per-Gaussian backward on the same stream
+  camera_header(cv, 1, P, cam, bwd_error, means3D, scales, rotations, cov3D_precomp, shs);
+  camera_view(cv.v[0], cam, *cg, (double*)cam_scratch, radii, &g, partials, dL_dz, im.final_T, g.clamped, num_rendered, dL_dcolor);
+  return gsr_launch_camera_bwd(cv, cam.antialiasing != 0, st);
 }
 extern "C" {
 int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
@@ -562,7 +597,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw,
-                          const float* const* dL_ddepth_views, const float* const* dL_dalpha_views, void* stream);
+                          const float* const* dL_ddepth_views, const float* const* dL_dalpha_views, void* stream,
+                          const gsr_camera_grads* cams = nullptr, void* cam_scratch = nullptr);
 extern "C" {
 int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
@@ -584,6 +620,18 @@ int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, co
   return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
                       image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
                       dL_dcov3D, dL_dsh, dL_ddepth, dL_dalpha, stream);
+}
+
+int gsr_backward_cam(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
+                     const float* dL_dalpha, const gsr_camera_grads* cam, void* cam_scratch, void* stream) {
+  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
+                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                      dL_dcov3D, dL_dsh, dL_ddepth, dL_dalpha, stream, cam, cam_scratch);
 }
 
 int gsr_alpha_views(int32_t V, int32_t H, int32_t W, void* const* image_states, float* out_alpha, void* stream) {
@@ -779,6 +827,20 @@ int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const ui
                         stream);
 }
 
+int gsr_backward_batch_cam(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                           const float* scales, const float* rotations, const float* colors_precomp,
+                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                           void* const* binning_states, void* const* image_states, void* batch_state,
+                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                           const float* const* dL_dalpha_views, const gsr_camera_grads* cams, void* cam_scratch, void* stream) {
+  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, dL_dalpha_views,
+                        stream, cams, cam_scratch);
+}
+
 int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp,
                        const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
@@ -803,9 +865,11 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
                        float* const* dL_dmeans2D,
                        float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
                        float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, const float* const* dL_ddepth_views,
-                       const float* const* dL_dalpha_views, void* stream) {
-  GsrRange _range(dL_ddepth_views ? "gsr_backward_batch_depth" : (dL_dalpha_views ? "gsr_backward_batch_alpha" : "gsr_backward_batch"));
+                       const float* const* dL_dalpha_views, void* stream, const gsr_camera_grads* cams, void* cam_scratch) {
+  GsrRange _range(cams ? "gsr_backward_batch_cam" : (dL_ddepth_views ? "gsr_backward_batch_depth"
+                                                                     : (dL_dalpha_views ? "gsr_backward_batch_alpha" : "gsr_backward_batch")));
   if (int rc = check_batch("gsr_backward_batch", V, s, batch_state)) return rc;
+  if (cams && (!cam_scratch || raw)) { gsr_set_error("gsr_backward_batch_cam: NULL cam_scratch, or raw parameters"); return -2; }
   if (int rc = check_geometry_of(V, geometry_of)) return rc;
   if (!num_rendered || !radii || !geom_states || !binning_states || !image_states || !dL_dcolor || !scratch ||
       !dL_dmeans3D || !dL_dmeans2D || (!dL_dopacity && !raw) || !means3D) {
@@ -817,7 +881,20 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
     gsr_set_error("gsr_backward_batch (raw parameters): NULL pointer or cov3D_precomp given");
     return -2;
   }
-  if (P <= 0) return 0;
+  if (P <= 0) {   // nothing blended: every view is its background (T = 1), every other camera gradient is 0
+    if (!cams) return 0;
+    GsrCamViews cv;
+    GsrCam cam0;
+    if (int rc = make_cam(&s[0], &cam0)) return rc;
+    camera_header(cv, V, 0, cam0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    for (int v = 0; v < V; ++v) {
+      GsrCam cam;
+      if (int rc = make_cam(&s[v], &cam)) return rc;
+      camera_view(cv.v[v], cam, cams[v], (double*)cam_scratch + (size_t)v * cv.nblk * GSR_CAM_ROW, nullptr, nullptr, nullptr, nullptr,
+                  nullptr, nullptr, 0, dL_dcolor[v]);
+    }
+    return gsr_launch_camera_bwd(cv, false, (hipStream_t)stream);
+  }
   hipStream_t st = (hipStream_t)stream;
   BatchState b;
   gsr_carve_batch(batch_state, V, P, s[0].image_height, s[0].image_width, &b);
@@ -845,7 +922,8 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
   GsrDepthViews dv;
   GsrAaViews av;          // anti-aliasing: every view's records (staged o'); check_batch made the views agree on the bit
   const bool aa = (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING) != 0;
-  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth;
+  // (the camera pass needs each view's own records: camera gradients run unfused, as the depth build does)
+  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth && !cams;
   if (!fuse_bwd)
     for (int v = 0; v < V; ++v) { partner[v] = -1; fused[v] = 0; }
   for (int v = 0; v < V; ++v) {
@@ -898,9 +976,27 @@ static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uin
     }
   }
   (void)colors_precomp;
-  return gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
-                                         dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st, (depth && any) ? &dvp : nullptr,
-                                         aa ? &av : nullptr);
+  if (int rc = gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
+                                               dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st,
+                                               (depth && any) ? &dvp : nullptr, aa ? &av : nullptr))
+    return rc;
+  if (!cams) return 0;
+  // the camera pass: one launch for every view (blockIdx.y), each view's own records (the call ran unfused)
+  GsrCamViews cv;
+  GsrCam cam0;
+  if (int rc = make_cam(&s[0], &cam0)) return rc;
+  camera_header(cv, V, P, cam0, vw.bwd_error, means3D, scales, rotations, cov3D_precomp, nullptr);
+  double* slab = (double*)cam_scratch;
+  for (int v = 0; v < V; ++v) {
+    GsrCam cam;
+    if (int rc = make_cam(&s[v], &cam)) return rc;
+    GeomState g; ImageState im;
+    gsr_carve_geom(geom_states[v], P, &g);
+    gsr_carve_image(image_states[v], cam.H, cam.W, &im);
+    camera_view(cv.v[v], cam, cams[v], slab + (size_t)v * cv.nblk * GSR_CAM_ROW, radii[v], &g, vw.v[v].partials,
+                depth ? dvp.dL_dz[v] : nullptr, im.final_T, nullptr, num_rendered[v], dL_dcolor[v]);
+  }
+  return gsr_launch_camera_bwd(cv, aa, st);
 }
 extern "C" {
 

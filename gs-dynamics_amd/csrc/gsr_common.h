@@ -347,6 +347,43 @@ int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_mo
                                     float* dL_dmeans3D, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
                                     float* dL_drotations, float* dL_dcov3D, hipStream_t st, const GsrDepthViews* depth = nullptr,
                                     const GsrAaViews* aa = nullptr);
+// Camera gradients (gsr_backward_cam / gsr_backward_batch_cam): the camera pass behind the per-Gaussian backward.
+// Its own compact per-view table (GsrBwdViews is close to the 4 KB kernel-argument limit).
+struct GsrCamView {
+  const float *view, *proj, *campos;
+  const int32_t* radii;
+  const uint8_t* used; const uint32_t* tracked;   // see GsrBwdView
+  const uint32_t* offsets;
+  const float4* partials;
+  const float* dL_dz;        // the depth build's per-entry dL/dz of this view, or nullptr (no depth gradient)
+  const float4* rec;         // anti-aliasing: the forward's records (staged o'), else unused
+  const uint32_t* clamped;   // SH: GeomState::clamped, else unused
+  const float* final_T;      // this view's image state (nullptr: nothing blended, T = 1)
+  const float* dL_dcolor;    // the incoming colour gradient [3,H,W] (nullptr: no bg gradient wanted)
+  double* slab;              // [nblk][GSR_CAM_ROW] fp64 block rows of this view (the camera scratch)
+  float *out_view, *out_proj, *out_campos, *out_bg;   // gsr_camera_grads of this view (nullptr members: not wanted)
+  uint32_t cap;              // entries the record buffer holds (reads are clamped to it)
+  int W, H;
+  float tanfovx, tanfovy;
+};
+struct GsrCamViews {
+  int V, P, nblk, sh_degree, M;
+  float mod;
+  const uint32_t* bwd_error;   // the call's GSR_QUEUE_BWD_ERROR word (or nullptr): != 0 -> the camera outputs are written as NaN
+  const float *means3D, *scales, *rotations, *cov3D, *shs;
+  GsrCamView v[GSR_MAX_BATCH];
+};
+static_assert(sizeof(GsrCamViews) + 64 <= 4096, "camera_bwd kernel arguments above 4 KB");
+#define GSR_CAM_ROW 32   // doubles per slab row (30 terms, padded)
+// blocks of the camera pass per view: one per 256 Gaussians, and at least one per 256 pixels up to 256 blocks (the bg sums)
+static inline int gsr_camera_blocks(int P, int H, int W) {
+  const long long g = ((long long)(P > 0 ? P : 0) + GSR_BLOCK - 1) / GSR_BLOCK;
+  long long px = ((long long)(H > 0 ? H : 0) * (W > 0 ? W : 0) + GSR_BLOCK - 1) / GSR_BLOCK;
+  if (px > 256) px = 256;
+  const long long n = g > px ? g : px;
+  return (int)(n > 0 ? n : 1);
+}
+int gsr_launch_camera_bwd(const GsrCamViews& cv, bool antialiasing, hipStream_t st);
 int gsr_launch_image_loss_fwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, float* fA,
                               float* fC, float* fE, float* block_l1, float* block_ssim, hipStream_t st);
 int gsr_launch_image_loss_bwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, const float* fA,

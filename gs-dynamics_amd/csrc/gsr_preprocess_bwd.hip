@@ -26,6 +26,8 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v 
 
 // SH backward for one Gaussian: writes dL_dsh (all M coefficients; inactive ones get 0) and returns
 // the gradient w.r.t. the mean through the view direction.
+// NO_DSH (the camera pass): only the mean term, dL_dsh is not written (dsh may be nullptr).  dL/dcampos = -dmean.
+template <bool NO_DSH = false>
 __device__ void sh_backward(int deg, int M, const float* __restrict__ sh, float3 p, const float* __restrict__ campos,
                             uint32_t clamped, float g0, float g1, float g2, float* __restrict__ dsh, float dmean[3]) {
   float dL[3] = {(clamped & 1u) ? 0.f : g0, (clamped & 2u) ? 0.f : g1, (clamped & 4u) ? 0.f : g2};
@@ -78,7 +80,7 @@ __device__ void sh_backward(int deg, int M, const float* __restrict__ sh, float3
     }
   }
   const int ncoef = (deg + 1) * (deg + 1);
-  for (int k = 0; k < M; ++k) {
+  for (int k = 0; !NO_DSH && k < M; ++k) {
     const float bk = k < ncoef ? basis[k < 16 ? k : 15] : 0.f;
     dsh[k * 3 + 0] = bk * dL[0]; dsh[k * 3 + 1] = bk * dL[1]; dsh[k * 3 + 2] = bk * dL[2];
   }
@@ -230,12 +232,20 @@ __device__ __forceinline__ float aa_ratio32(const float* __restrict__ view, int 
 // reaches dL/dmeans3D as gz * (view[2], view[6], view[10]) inside the fp64 sum.
 // AA: the staged opacity was o' = o c(A, B, C).  c32 = the forward's fp32 3D covariance (build_cov3_f32), o_s = this
 // view's staged o'; the term o g dc/d{A, B, C} (g = ps.gop = dL/do') joins dL/d{a, b, c}, and *c_out receives the factor of dL/do = c g.
-template <bool DEPTH = false, bool AA = false>
+// CAM (the camera pass): *ct receives the fp64 intermediates the camera gradients are made of.
+struct ChainTerms {
+  real dt[3];             // dL/d(view-space position): frustum-clamp mask, depth and anti-aliasing terms included
+  real dT0[3], dT1[3];    // dL/dT, T = J W (the two rows)
+  real J00, J02, J11, J12;
+  real m2x, m2y;          // dL/d(NDC mean)
+  real hx, hy, mw;        // the projection: h = proj p, mw = 1 / (h.w + 1e-7)
+};
+template <bool DEPTH = false, bool AA = false, bool CAM = false>
 __device__ __forceinline__ void view_chain(const float* __restrict__ view, const float* __restrict__ proj, int W, int H,
                                            float tanfovx, float tanfovy, float3 p, const real c[6],
                                            const PartialSum& ps, float gcov[6], float gm3[3], float gm2[2],
                                            float sx_first = 0.f, float sy_first = 0.f, float* gm2_first = nullptr, float gz = 0.f,
-                                           const float* c32 = nullptr, float o_s = 0.f, float* c_out = nullptr) {
+                                           const float* c32 = nullptr, float o_s = 0.f, float* c_out = nullptr, ChainTerms* ct = nullptr) {
   // The frustum clamp is the forward's decision: the fp32 view-space position, txtz / tytz and limit, with the forward's operations in its
   // order (both files build with contraction off, so these are its bits).  An fp64 txtz within ~1e-7 of the limit can fall on the other
   // side, and then dtx / dty would be dropped or added in full.  A clamped coordinate sits at the forward's fp32 limit, widened.
@@ -340,6 +350,13 @@ __device__ __forceinline__ void view_chain(const float* __restrict__ view, const
   gm3[0] += (float)(view[0] * dtx + view[1] * dty + view[2] * dtz + (proj[0] * mw - proj[3] * mul1) * m2x + (proj[1] * mw - proj[3] * mul2) * m2y);
   gm3[1] += (float)(view[4] * dtx + view[5] * dty + view[6] * dtz + (proj[4] * mw - proj[7] * mul1) * m2x + (proj[5] * mw - proj[7] * mul2) * m2y);
   gm3[2] += (float)(view[8] * dtx + view[9] * dty + view[10] * dtz + (proj[8] * mw - proj[11] * mul1) * m2x + (proj[9] * mw - proj[11] * mul2) * m2y);
+  if (CAM) {
+    ct->dt[0] = dtx; ct->dt[1] = dty; ct->dt[2] = dtz;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { ct->dT0[j] = dT0[j]; ct->dT1[j] = dT1[j]; }
+    ct->J00 = J00; ct->J02 = J02; ct->J11 = J11; ct->J12 = J12;
+    ct->m2x = m2x; ct->m2y = m2y; ct->hx = hx; ct->hy = hy; ct->mw = mw;
+  }
 }
 
 // dL/dcov3D -> dL/dscale, dL/drotation (linear in gcov: in the multi-view kernel it runs once on the sum).
@@ -389,6 +406,9 @@ __device__ __forceinline__ bool gsr_view_used(const GsrBwdView& w, int i) {
 #include "gsr_preprocess_bwd_kernels.inc"
 #undef GSR_PBWD_DEPTH
 #undef GSR_PBWD_AA
+
+// the camera pass: camera_bwd_kernel<USE_SH, AA>, camera_reduce_kernel
+#include "gsr_camera_bwd.inc"
 
 }  // namespace gsr_preprocess_bwd
 using namespace gsr_preprocess_bwd;
@@ -487,6 +507,25 @@ int gsr_launch_preprocess_bwd_views(const GsrBwdViews& vw, int P, float scale_mo
     hipLaunchKernelGGL(preprocess_bwd_views_kernel, dim3((P + GSR_BLOCK - 1) / GSR_BLOCK), dim3(GSR_BLOCK), 0, st, vw, P,
                        scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D, dL_dcolors, dL_dopacity,
                        dL_dscales, dL_drotations, dL_dcov3D); }
+  GSR_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int gsr_launch_camera_bwd(const GsrCamViews& cv, bool antialiasing, hipStream_t st) {
+  if (cv.V <= 0) return 0;
+  {
+    GSR_PROF("camera_bwd", st);
+    const dim3 grid(cv.nblk, cv.V), block(GSR_BLOCK);
+    if (cv.shs && antialiasing) hipLaunchKernelGGL((camera_bwd_kernel<true, true>), grid, block, 0, st, cv);
+    else if (cv.shs) hipLaunchKernelGGL((camera_bwd_kernel<true, false>), grid, block, 0, st, cv);
+    else if (antialiasing) hipLaunchKernelGGL((camera_bwd_kernel<false, true>), grid, block, 0, st, cv);
+    else hipLaunchKernelGGL((camera_bwd_kernel<false, false>), grid, block, 0, st, cv);
+  }
+  GSR_HIP_CHECK(hipGetLastError());
+  {
+    GSR_PROF("camera_reduce", st);
+    hipLaunchKernelGGL(camera_reduce_kernel, dim3(cv.V), dim3(GSR_BLOCK), 0, st, cv);
+  }
   GSR_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -269,16 +269,20 @@ rasterize_gaussians(const torch::Tensor& background, const torch::Tensor& means3
 //           projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer)
 //           -> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 // (image height / width travel in upstream's dL_dout_color shape: here too)
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
-rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
-                             const torch::Tensor& scales, const torch::Tensor& rotations, double scale_modifier, const torch::Tensor& cov3D_precomp,
-                             const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, double tan_fovx, double tan_fovy,
-                             const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
-                             const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                             bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
-                             const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W], the depth build
-                             const c10::optional<torch::Tensor>& dL_dout_alpha,    // extension (default None): [1, H, W], the alpha term
-                             bool antialiasing) {  // extension (default false): the forward's GSR_SETTINGS_ANTIALIASING
+// Camera gradients: which of dL/d(bg, viewmatrix, projmatrix, campos) the node wants, and where they go ([3], [16],
+// [16], [3] fp32 on the render device; undefined = not wanted)
+struct CameraGrads { bool want[4] = {false, false, false, false}; torch::Tensor out[4]; };
+
+typedef std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+    BackwardGrads;
+BackwardGrads
+backward_body(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+              const torch::Tensor& scales, const torch::Tensor& rotations, double scale_modifier, const torch::Tensor& cov3D_precomp,
+              const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, double tan_fovx, double tan_fovy,
+              const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
+              const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+              bool want_color_grad, const c10::optional<torch::Tensor>& dL_dout_depth, const c10::optional<torch::Tensor>& dL_dout_alpha,
+              bool antialiasing, CameraGrads* camg) {
   const c10::Device dev = means3D.device();
   c10::hip::HIPGuard guard(dev.index());
   const int64_t P = means3D.size(0);
@@ -286,6 +290,20 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   TORCH_CHECK(dL_dout_color.dim() == 3 && dL_dout_color.size(0) == 3, "dL_dout_color must be [3, H, W]");
   const int64_t H = dL_dout_color.size(1), W = dL_dout_color.size(2);
   auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+  const bool cam_on = camg && (camg->want[0] || camg->want[1] || camg->want[2] || camg->want[3]);
+  gsr_camera_grads cg = {nullptr, nullptr, nullptr, nullptr};
+  torch::Tensor cam_scratch;
+  if (cam_on) {
+    static const int64_t n[4] = {3, 16, 16, 3};
+    for (int k = 0; k < 4; ++k)
+      if (camg->want[k]) camg->out[k] = torch::empty({n[k]}, f32);
+    cg.dL_dbg = camg->want[0] ? camg->out[0].data_ptr<float>() : nullptr;
+    cg.dL_dviewmatrix = camg->want[1] ? camg->out[1].data_ptr<float>() : nullptr;
+    cg.dL_dprojmatrix = camg->want[2] ? camg->out[2].data_ptr<float>() : nullptr;
+    cg.dL_dcampos = camg->want[3] ? camg->out[3].data_ptr<float>() : nullptr;
+    cam_scratch = torch::empty({(int64_t)gsr_camera_scratch_bytes(1, (int32_t)P, (int32_t)H, (int32_t)W)},
+                               torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+  }
   torch::Tensor d_means3D = torch::empty({P, 3}, f32), d_means2D = torch::empty({P, 3}, f32), d_opacity = torch::empty({P, 1}, f32);
   torch::Tensor d_colors = (M || !want_color_grad) ? torch::empty({0}, f32) : torch::empty({P, 3}, f32);
   torch::Tensor d_cov = torch::empty({P, 6}, f32);
@@ -293,7 +311,18 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   const bool has_sr = scales.numel() > 0;
   torch::Tensor d_scales = has_sr ? torch::empty({P, 3}, f32) : torch::empty({0}, f32);
   torch::Tensor d_rot = has_sr ? torch::empty({P, 4}, f32) : torch::empty({0}, f32);
-  if (P == 0) return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
+  if (P == 0) {
+    if (cam_on) {   // nothing blended: dL/dbg = the sum of dL/dC, the rest 0
+      Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev,
+                                  antialiasing);
+      const torch::Tensor g = f32c(dL_dout_color, dev);
+      check(gsr_backward_cam(&st.s, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             g.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                             nullptr, &cg, cam_scratch.data_ptr(), (void*)c10::hip::getCurrentHIPStream(dev.index()).stream()),
+            "gsr_backward_cam");
+    }
+    return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
+  }
   {
     auto want = [&](const torch::Tensor& t, int64_t n, const char* name) {
       TORCH_CHECK(t.numel() == 0 || t.numel() == n, "rasterize_gaussians_backward: ", name, " must hold ", n, " elements, got ", t.numel());
@@ -320,13 +349,38 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
   torch::Tensor scratch = torch::empty({(int64_t)(has_depth ? gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)
                                                              : gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R))},
                                        torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-  check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
-                         radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
-                         g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
-                         optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
-                         has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
-        "gsr_backward_ext");
+  // camera gradients: gsr_backward_cam (gsr_backward_ext plus the camera pass); without them, gsr_backward_ext as before
+  if (cam_on)
+    check(gsr_backward_cam(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
+                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, &cg,
+                           cam_scratch.data_ptr(), stream),
+          "gsr_backward_cam");
+  else
+    check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
+                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
+          "gsr_backward_ext");
   return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
+}
+
+BackwardGrads
+rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                             const torch::Tensor& scales, const torch::Tensor& rotations, double scale_modifier, const torch::Tensor& cov3D_precomp,
+                             const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, double tan_fovx, double tan_fovy,
+                             const torch::Tensor& dL_dout_color, const torch::Tensor& sh, int64_t degree, const torch::Tensor& campos,
+                             const torch::Tensor& geomBuffer, int64_t R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                             bool want_color_grad,   // extension over upstream (default true): false = colours_precomp needs no gradient
+                             const c10::optional<torch::Tensor>& dL_dout_depth,    // extension (default None): [1, H, W], the depth build
+                             const c10::optional<torch::Tensor>& dL_dout_alpha,    // extension (default None): [1, H, W], the alpha term
+                             bool antialiasing) {  // extension (default false): the forward's GSR_SETTINGS_ANTIALIASING
+  return backward_body(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                       tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, want_color_grad, dL_dout_depth,
+                       dL_dout_alpha, antialiasing, nullptr);
 }
 
 // ---- the autograd node of one GaussianRasterizer call, in C++ (round 5).  The Python wrapper used to be a
@@ -342,8 +396,9 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
                                                 torch::Tensor rotations, torch::Tensor cov3D, torch::Tensor bg, torch::Tensor viewmatrix,
                                                 torch::Tensor projmatrix, torch::Tensor campos, double tanfovx, double tanfovy, int64_t H,
                                                 int64_t W, double scale_modifier, int64_t degree, bool prefiltered, bool will_backward,
-                                                bool differentiable_depth, bool return_alpha, bool antialiasing) {
+                                                bool differentiable_depth, bool return_alpha, bool antialiasing, bool camera_gradients) {
     (void)means2D;
+    ctx->saved_data["camera"] = camera_gradients;   // out[8..11]: dL/d(bg, viewmatrix, projmatrix, campos), DESIGN.md section 3g
     // grad_depth is ignored unless differentiable_depth, an unused alpha has no gradient: do not let autograd fill zero images for them
     ctx->set_materialize_grads(false);
     ctx->saved_data["depth"] = differentiable_depth;
@@ -373,11 +428,23 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     return {color, radii, depth};
   }
   static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads) {
-    torch::autograd::variable_list out(23);       // one slot per forward argument; undefined = no gradient
-    if (ctx->saved_data["empty"].toBool()) return out;
+    torch::autograd::variable_list out(24);       // one slot per forward argument; undefined = no gradient
+    // camera gradients (opt-in): the four settings tensors that need one
+    CameraGrads camg;
+    const bool camera = ctx->saved_data["camera"].toBool();
+    for (int k = 0; camera && k < 4; ++k) camg.want[k] = ctx->needs_input_grad(8 + k);
+    const bool cam_on = camg.want[0] || camg.want[1] || camg.want[2] || camg.want[3];
+    if (ctx->saved_data["empty"].toBool() && !cam_on) return out;
     const auto sv = ctx->get_saved_variables();
     const torch::Tensor &m3 = sv[0], &radii = sv[1], &col = sv[2], &sh = sv[3], &sc = sv[4], &rot = sv[5], &cov = sv[6], &geom = sv[7],
                         &binning = sv[8], &image = sv[9], &bg = sv[10], &view = sv[11], &proj = sv[12], &campos = sv[13];
+    // each camera gradient has the shape, dtype and device of the tensor the caller passed (a [1,4,4] transposed view included: the
+    // kernels index the matrices in their logical, contiguous order)
+    auto put_camera = [&]() {
+      const torch::Tensor* in[4] = {&bg, &view, &proj, &campos};
+      for (int k = 0; k < 4; ++k)
+        if (camg.want[k]) out[8 + k] = camg.out[k].reshape(in[k]->sizes()).to(in[k]->options());
+    };
     const int64_t H = ctx->saved_data["H"].toInt(), W = ctx->saved_data["W"].toInt();
     torch::Tensor g = grads[0];                   // grads[1] (radii): accepted, ignored -- no reference call site differentiates it
     // grads[2] (depth): ignored unless the call opted in (differentiable_depth); then the depth build -- when autograd delivers one
@@ -390,10 +457,12 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     const bool has_sh = ctx->saved_data["has_sh"].toBool(), has_col = ctx->saved_data["has_col"].toBool(),
                has_sc = ctx->saved_data["has_sc"].toBool(), has_cov = ctx->saved_data["has_cov"].toBool();
     const bool want_col = has_col && ctx->needs_input_grad(3);      // frozen colours (the reference's training): the six-sum backward
-    auto r = rasterize_gaussians_backward(bg, m3, radii, col, sc, rot, ctx->saved_data["scale_modifier"].toDouble(), cov, view, proj,
-                                          ctx->saved_data["tanfovx"].toDouble(), ctx->saved_data["tanfovy"].toDouble(), g, sh,
-                                          ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd, ga,
-                                          ctx->saved_data["antialiasing"].toBool());
+    auto r = backward_body(bg, m3, radii, col, sc, rot, ctx->saved_data["scale_modifier"].toDouble(), cov, view, proj,
+                           ctx->saved_data["tanfovx"].toDouble(), ctx->saved_data["tanfovy"].toDouble(), g, sh,
+                           ctx->saved_data["degree"].toInt(), campos, geom, ctx->saved_data["R"].toInt(), binning, image, want_col, gd, ga,
+                           ctx->saved_data["antialiasing"].toBool(), cam_on ? &camg : nullptr);
+    if (cam_on) put_camera();
+    if (ctx->saved_data["empty"].toBool()) return out;   // P = 0: the camera gradients only
     out[0] = std::get<3>(r);                      // means3D
     out[1] = std::get<0>(r);                      // means2D (x, y in NDC units, z = 0)
     if (has_sh) out[2] = std::get<5>(r);
@@ -417,18 +486,29 @@ rasterize(const std::shared_ptr<LayerState>& state,      // the calling module's
           double tanfovx, double tanfovy, int64_t H, int64_t W, double scale_modifier, int64_t degree, bool prefiltered,
           bool differentiable_depth,     // extension: the depth output is differentiated too (the depth build)
           bool return_alpha,             // extension: a fourth output, the rendered alpha 1 - final_T (differentiable)
-          bool antialiasing) {           // extension: the opacity compensation (GSR_SETTINGS_ANTIALIASING)
+          bool antialiasing,             // extension: the opacity compensation (GSR_SETTINGS_ANTIALIASING)
+          bool camera_gradients) {       // extension: dL/d(bg, viewmatrix, projmatrix, campos)
+  if (camera_gradients)   // the camera pass reads exactly these many floats: a wrongly sized tensor is an error, not a truncation
+    TORCH_CHECK(bg.numel() == 3 && viewmatrix.numel() == 16 && projmatrix.numel() == 16 && campos.numel() == 3,
+                "rasterize(camera_gradients=True): bg / campos must hold 3 floats and viewmatrix / projmatrix 16, got ", bg.numel(), ", ",
+                viewmatrix.numel(), ", ", projmatrix.numel(), ", ", campos.numel());
   bool will_backward = false;
-  if (at::GradMode::is_enabled())
+  if (at::GradMode::is_enabled()) {
     for (const torch::Tensor* t : {&means3D, &means2D, &sh, &colors, &opacities, &scales, &rotations, &cov3D})
       will_backward = will_backward || (t->defined() && t->requires_grad());
+    // pose-only optimisation (frozen Gaussians, trainable camera): the forward must keep what a backward reads (no GSR_FORWARD_ONLY)
+    if (camera_gradients)
+      for (const torch::Tensor* t : {&bg, &viewmatrix, &projmatrix, &campos})
+        will_backward = will_backward || (t->defined() && t->requires_grad());
+  }
   struct Scope {      // the node's forward runs inside apply(), on this thread: it finds the state here
     LayerState* prev;
     explicit Scope(LayerState* s) : prev(t_call_state) { t_call_state = s; }
     ~Scope() { t_call_state = prev; }
   } scope(state.get());
   auto o = RasterizeFn::apply(means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, bg, viewmatrix, projmatrix, campos, tanfovx,
-                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth, return_alpha, antialiasing);
+                              tanfovy, H, W, scale_modifier, degree, prefiltered, will_backward, differentiable_depth, return_alpha, antialiasing,
+                              camera_gradients);
   if (return_alpha) return pybind11::make_tuple(o[0], o[1], o[2], o[3]);
   return pybind11::make_tuple(o[0], o[1], o[2]);
 }
@@ -484,7 +564,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rasterize", &rasterize, py::arg("state"), py::arg("means3D"), py::arg("means2D"), py::arg("sh"), py::arg("colors"), py::arg("opacities"),
         py::arg("scales"), py::arg("rotations"), py::arg("cov3D"), py::arg("bg"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"),
         py::arg("tanfovx"), py::arg("tanfovy"), py::arg("H"), py::arg("W"), py::arg("scale_modifier"), py::arg("degree"), py::arg("prefiltered"),
-        py::arg("differentiable_depth") = false, py::arg("return_alpha") = false, py::arg("antialiasing") = false);
+        py::arg("differentiable_depth") = false, py::arg("return_alpha") = false, py::arg("antialiasing") = false,
+        py::arg("camera_gradients") = false);
   m.def("mark_visible", &mark_visible);
   m.def("abi_version", []() { return (int)GSR_VERSION; });   // the header this layer was COMPILED against (compare with the library's gsr_version())
 }

@@ -104,10 +104,39 @@ def _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_):
 
 
 def _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales, d_rot, d_cov):
-    """One gradient slot per apply() argument: None for the inputs the call did not have and for the settings and the two switches."""
+    """One gradient slot per apply() argument: None for the inputs the call did not have and for the settings and the switches."""
     has_sh, has_col, has_sc, has_cov = ctx.has
     return (d_means3D, d_means2D, d_sh if has_sh else None, d_colors if has_col else None, d_opacity, d_scales if has_sc else None,
-            d_rot if has_sc else None, d_cov if has_cov else None, None, None, None, None)
+            d_rot if has_sc else None, d_cov if has_cov else None, None, None, None, None, None)
+
+
+_CAMERA_FIELDS = ("bg", "viewmatrix", "projmatrix", "campos")   # the settings tensors camera_gradients differentiates, in apply() order
+_CAMERA_NUMEL = (3, 16, 16, 3)
+
+
+def _camera_tensors(settings_list):
+    """The trailing apply() arguments of a camera_gradients call: (bg, viewmatrix, projmatrix, campos) of every view, checked."""
+    out = []
+    for rs in settings_list:
+        for name, n in zip(_CAMERA_FIELDS, _CAMERA_NUMEL):
+            t = getattr(rs, name)
+            if not isinstance(t, torch.Tensor) or t.numel() != n:
+                raise ValueError(f"camera_gradients=True: raster_settings.{name} must be a tensor of {n} elements, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            out.append(t)
+    return out
+
+
+def _camera_grads(ctx, cam_out, v):
+    """The gradients of view v's four camera arguments (apply() slots 13 + 4 v ...): each in the shape, dtype and device the caller
+    passed; None where none is needed."""
+    grads = []
+    for k in range(4):
+        shape, dtype, device = ctx.cam_meta[4 * v + k]
+        g = cam_out[k] if cam_out is not None else None
+        need = ctx.needs_input_grad[13 + 4 * v + k]
+        grads.append(g.reshape(shape).to(dtype=dtype, device=device) if (need and g is not None) else None)
+    return grads
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -116,11 +145,14 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False):
+                raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False, camera_gradients=False, *camera):
         # grad_depth is ignored unless differentiable_depth: do not let autograd fill a zero image for it (or for an unused colour / alpha)
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
         ctx.alpha = bool(return_alpha)
+        # camera_gradients: `camera` = (bg, viewmatrix, projmatrix, campos) of raster_settings, the trailing apply() arguments
+        ctx.camera = bool(camera_gradients)
+        ctx.cam_meta = [(t.shape, t.dtype, t.device) for t in camera]
         m3 = _prep(means3D)
         if m3 is None:
             if means3D is not None and means3D.dim() == 2 and means3D.shape[1] == 3:
@@ -128,6 +160,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 dev = means3D.device
                 H, W = int(raster_settings.image_height), int(raster_settings.image_width)
                 ctx.empty = True
+                if ctx.camera:    # the backward's dL/dbg needs the settings (nothing was blended: the sum of dL/dC)
+                    ctx.state = _hip.empty_state(raster_settings, dev)
                 return (torch.zeros((3, H, W), device=dev), torch.zeros((0,), dtype=torch.int32, device=dev),
                         torch.zeros((1, H, W), device=dev)) + ((torch.zeros((1, H, W), device=dev),) if ctx.alpha else ())
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -148,19 +182,31 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha=None):
         # grad_radii: accepted, ignored; grad_depth: used with differentiable_depth; grad_alpha: used whenever autograd delivers one
+        want = tuple(ctx.needs_input_grad[13 + k] for k in range(4)) if ctx.camera else None
+        if want is not None and not any(want):
+            want = None
+        cam = {} if want is None else {"camera_grads": want}
         if ctx.empty:
-            return (None,) * 12
+            if want is None:
+                return (None,) * (13 + len(ctx.cam_meta))
+            H, W = ctx.state.H, ctx.state.W
+            g = grad_color if grad_color is not None else torch.zeros((3, H, W), device=ctx.state.keep[0].device)
+            cam_out = _hip.rasterize_backward(ctx.state, g, ctx.state.keep[0].new_empty((0, 3)), None, None, None, None, None, None,
+                                              **cam)[8]
+            return (None,) * 13 + tuple(_camera_grads(ctx, cam_out, 0))
         m3, radii, col_, sh_, sc_, rot_, cov_ = ctx.saved_tensors
         has_sh, has_col, has_sc, has_cov = ctx.has
         if grad_color is None:
             grad_color = torch.zeros((3, ctx.state.H, ctx.state.W), device=m3.device)
-        d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh = _hip.rasterize_backward(
+        r = _hip.rasterize_backward(
             ctx.state, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
             want_color_grad=bool(has_col and ctx.needs_input_grad[3]),
             **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}),
-            **({} if grad_alpha is None else {"grad_alpha": grad_alpha}))
-        return _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales, d_rot, d_cov)
+            **({} if grad_alpha is None else {"grad_alpha": grad_alpha}), **cam)
+        d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh = r[:8]
+        return _input_grads(ctx, d_means3D, d_means2D, d_sh, d_colors, d_opacity, d_scales, d_rot, d_cov) + \
+            tuple(_camera_grads(ctx, r[8] if want is not None else None, 0) if ctx.camera else ())
 
 
 class _RasterizeGaussiansViews(torch.autograd.Function):
@@ -171,10 +217,13 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
-                differentiable_depth=False, return_alpha=False, antialiasing=False):
+                differentiable_depth=False, return_alpha=False, antialiasing=False, camera_gradients=False, *camera):
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
         ctx.alpha = bool(return_alpha)
+        # camera_gradients: `camera` = (bg, viewmatrix, projmatrix, campos) of every view in turn, the trailing apply() arguments
+        ctx.camera = bool(camera_gradients)
+        ctx.cam_meta = [(t.shape, t.dtype, t.device) for t in camera]
         m3 = _prep(means3D)
         if m3 is None or m3.dim() != 2 or m3.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
@@ -198,26 +247,39 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         V = len(ctx.states)
         if grad_color is None:
             grad_color = torch.zeros((V, 3, ctx.states[0].H, ctx.states[0].W), device=m3.device)
-        d3, d2, dc, do, ds, dr, dcov, dsh = _hip.rasterize_backward_batch(
+        want = None
+        if ctx.camera:     # one flag per settings field: any view's tensor of that field needs a gradient
+            want = tuple(any(ctx.needs_input_grad[13 + 4 * v + k] for v in range(V)) for k in range(4))
+            if not any(want):
+                want = None
+        r = _hip.rasterize_backward_batch(
             ctx.states, grad_color, m3, radii, col_ if has_col else None, sh_ if has_sh else None,
             sc_ if has_sc else None, rot_ if has_sc else None, cov_ if has_cov else None,
             want_color_grad=bool(has_col and ctx.needs_input_grad[3]),
             **({"grad_depth": grad_depth} if (ctx.depth and grad_depth is not None) else {}),
-            **({"grad_alpha": grad_alpha} if grad_alpha is not None else {}))
+            **({"grad_alpha": grad_alpha} if grad_alpha is not None else {}),
+            **({} if want is None else {"camera_grads": want}))
+        d3, d2, dc, do, ds, dr, dcov, dsh = r[:8]
+        cam = []
+        for v in range(len(ctx.cam_meta) // 4):
+            cam += _camera_grads(ctx, r[8][v] if want is not None else None, v)
         # gradients arrive already summed over views (means2D stays per view); the state stays on ctx so that a
         # second backward (retain_graph=True) works, and is released with the graph
-        return _input_grads(ctx, d3, d2, dsh, dc, do, ds, dr, dcov)
+        return _input_grads(ctx, d3, d2, dsh, dc, do, ds, dr, dcov) + tuple(cam)
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False, antialiasing=False):
+                              rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False, antialiasing=False,
+                              camera_gradients=False):
     """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder.
     ``differentiable_depth``: the depth output [V,1,H,W] is differentiated too (see GaussianRasterizer); views that share a camera,
     which the backward otherwise fuses into one pass, are then differentiated unfused.
     ``return_alpha``: a fourth output, the rendered alpha [V,1,H,W] = 1 - final_T, always differentiable (see GaussianRasterizer); views
     that share a camera stay fused.  A view's ``means2D`` gradient then includes its own alpha term: a caller that wants a colour-only
     densification statistic must render alpha with a separate call (its own means2D holder).
-    ``antialiasing``: every view is rendered with the opacity compensation (see GaussianRasterizer)."""
+    ``antialiasing``: every view is rendered with the opacity compensation (see GaussianRasterizer).
+    ``camera_gradients``: every view's bg, viewmatrix, projmatrix and campos get their gradients (see GaussianRasterizer); views that
+    share a camera, which the backward otherwise fuses into one pass, are then differentiated unfused."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -237,7 +299,7 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
             empty if colors_precomp is None else (colors_precomp[lo:hi] if (per_view_col and not whole) else colors_precomp), opacities,
             empty if scales is None else scales, empty if rotations is None else rotations,
             empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth), bool(return_alpha),
-            bool(antialiasing))
+            bool(antialiasing), bool(camera_gradients), *(_camera_tensors(settings_list[lo:hi]) if camera_gradients else ()))
     if V <= _hip.MAX_BATCH:
         return call(0, V)
     # more views than one library call takes: several calls, outputs concatenated (autograd sums the shared inputs)
@@ -246,9 +308,10 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False):
+                        raster_settings, differentiable_depth=False, return_alpha=False, antialiasing=False, camera_gradients=False):
     """One view (upstream's entry point).  ``return_alpha``: a fourth output, the rendered alpha [1,H,W] (see GaussianRasterizer).
-    ``antialiasing``: the opacity compensation (see GaussianRasterizer)."""
+    ``antialiasing``: the opacity compensation (see GaussianRasterizer).  ``camera_gradients``: gradients for the settings' bg,
+    viewmatrix, projmatrix and campos (see GaussianRasterizer)."""
     native = _native() if (means3D is not None and means3D.is_cuda) else None
     if native is not None and not _PY_NODE:
         # one crossing into the torch C++ layer: forward and the autograd node live there (csrc/gsr_torch.cpp: RasterizeFn)
@@ -257,9 +320,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                 rs.projmatrix, rs.campos, float(rs.tanfovx), float(rs.tanfovy), int(rs.image_height), int(rs.image_width),
                                 float(rs.scale_modifier), int(rs.sh_degree), bool(rs.prefiltered),
                                 differentiable_depth=bool(differentiable_depth), return_alpha=bool(return_alpha),
-                                antialiasing=bool(antialiasing))
+                                antialiasing=bool(antialiasing), camera_gradients=bool(camera_gradients))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha), bool(antialiasing))
+                                     cov3Ds_precomp, raster_settings, bool(differentiable_depth), bool(return_alpha), bool(antialiasing),
+                                     bool(camera_gradients), *(_camera_tensors([raster_settings]) if camera_gradients else ()))
 
 
 class GaussianRasterizer(nn.Module):
@@ -282,15 +346,24 @@ class GaussianRasterizer(nn.Module):
     the fixed 0.3 px^2 dilation, so a Gaussian smaller than a pixel keeps the energy of its undilated footprint instead of being drawn too
     fat and too bright.  The opacity gradient is dL/do = c dL/d(o c), and the term through c reaches the covariance (scales / rotations or
     cov3D_precomp) and means3D.  Conic, radii, depth and the tile rects are unchanged.  Combines with ``differentiable_depth`` and
-    ``return_alpha``.  False: every output and gradient is bit for bit the plain render's.  """
+    ``return_alpha``.  False: every output and gradient is bit for bit the plain render's.  
+
+    ``camera_gradients`` (extension, default False): the settings' ``bg``, ``viewmatrix``, ``projmatrix`` and ``campos`` are
+    differentiated too, each gradient in the shape the caller passed (a [1,4,4] transposed view included), for pose refinement or camera
+    tracking against a frozen scene.  viewmatrix[3, 7, 11, 15] and projmatrix[2, 6, 10, 14] (column-major as stored) are never read by the
+    forward and get 0; campos reaches the render only through the SH view direction and gets 0 with precomputed colours.  ``tanfovx`` /
+    ``tanfovy`` are Python floats: no focal-length or field-of-view gradient is provided, although J depends on them.  Combines with the
+    three switches above.  False: a camera tensor that requires a gradient gets None, as upstream, and every output and gradient is bit
+    for bit the plain render's.  """
 
     def __init__(self, raster_settings: GaussianRasterizationSettings, differentiable_depth: bool = False, return_alpha: bool = False,
-                 antialiasing: bool = False):
+                 antialiasing: bool = False, camera_gradients: bool = False):
         super().__init__()
         self.raster_settings = raster_settings
         self.differentiable_depth = bool(differentiable_depth)
         self.return_alpha = bool(return_alpha)
         self.antialiasing = bool(antialiasing)
+        self.camera_gradients = bool(camera_gradients)
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         with torch.no_grad():
@@ -315,4 +388,4 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, rs, differentiable_depth=self.differentiable_depth, return_alpha=self.return_alpha,
-                                   antialiasing=self.antialiasing)
+                                   antialiasing=self.antialiasing, camera_gradients=self.camera_gradients)

@@ -64,6 +64,11 @@ class GsrRawParams(C.Structure):
                                           "d_unnorm_rotations", "d_logit_opacities", "d_log_scales")]
 
 
+class GsrCameraGrads(C.Structure):
+    """gsr_camera_grads of include/gsr.h: device pointers of one view's dL/d(viewmatrix [16], projmatrix [16], campos [3], bg [3])."""
+    _fields_ = [(n, C.c_void_p) for n in ("dL_dviewmatrix", "dL_dprojmatrix", "dL_dcampos", "dL_dbg")]
+
+
 EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes", "gsr_binning_bytes",
            "gsr_backward_scratch_bytes", "gsr_forward_preprocess", "gsr_forward_render", "gsr_backward",
            "gsr_forward_preprocess_same", "gsr_forward_render_shared", "gsr_forward_render_ex", "gsr_forward_render_shared_ex", "gsr_forward_capacity", "gsr_wait_block_counts",
@@ -78,7 +83,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_shared_terms_partials", "gsr_shared_terms_scratch", "gsr_shared_terms_forward", "gsr_shared_terms_backward",
            "gsr_activate_forward", "gsr_activate_backward", "gsr_adam_step", "gsr_radius_bookkeeping", "gsr_wait_counts",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
-           "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts")
+           "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
+           "gsr_camera_scratch_bytes", "gsr_backward_cam", "gsr_backward_batch_cam")
 
 
 def load_library():
@@ -136,6 +142,11 @@ def load_library():
     lib.gsr_backward_batch_ext.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, PV, vp]
     lib.gsr_alpha_views.restype = C.c_int
     lib.gsr_alpha_views.argtypes = [i32, i32, i32, PV, vp, vp]
+    lib.gsr_camera_scratch_bytes.restype = sz; lib.gsr_camera_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    lib.gsr_backward_cam.restype = C.c_int
+    lib.gsr_backward_cam.argtypes = lib.gsr_backward_ext.argtypes[:-1] + [C.POINTER(GsrCameraGrads), vp, vp]
+    lib.gsr_backward_batch_cam.restype = C.c_int
+    lib.gsr_backward_batch_cam.argtypes = lib.gsr_backward_batch_ext.argtypes[:-1] + [C.POINTER(GsrCameraGrads), vp, vp]
     lib.gsr_image_loss_blocks.restype = i32
     lib.gsr_image_loss_blocks.argtypes = [i32, i32, i32]
     lib.gsr_image_loss_forward.restype = C.c_int
@@ -369,15 +380,58 @@ def rasterize_forward(rs, means3D, opacities, colors_precomp, shs, scales, rotat
     return color, radii, depth, state
 
 
+CAMERA_SHAPES = (3, 16, 16, 3)   # dL/d(bg, viewmatrix, projmatrix, campos): the order of camera_grads
+
+
+def _camera_want(camera_grads):
+    """``camera_grads``: True (all four) or a sequence of four flags (bg, viewmatrix, projmatrix, campos) -> four bools."""
+    if camera_grads is True:
+        return (True,) * 4
+    want = tuple(bool(w) for w in camera_grads)
+    if len(want) != 4:
+        raise ValueError("camera_grads: True, or four flags (bg, viewmatrix, projmatrix, campos)")
+    return want
+
+
+def _camera_outputs(want, dev):
+    """(gsr_camera_grads record, (d_bg[3], d_view[16], d_proj[16], d_campos[3]) with None where not wanted)."""
+    outs = tuple(torch.empty((n,), dtype=torch.float32, device=dev) if w else None for w, n in zip(want, CAMERA_SHAPES))
+    return GsrCameraGrads(_ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(outs[0])), outs
+
+
+def empty_state(rs, dev) -> RasterState:
+    """The state of a P = 0 forward (nothing launched): its settings, for a camera-gradient backward (dL/dbg = the sum of dL/dC)."""
+    state = RasterState()
+    with _on(dev):
+        state.settings, state.keep = _make_settings(rs, dev, 0)
+    state.P, state.num_rendered, state.H, state.W = 0, 0, int(rs.image_height), int(rs.image_width)
+    state.geom = state.binning = state.image = state.pre = state.batch = state.geometry_of = state.pending = None
+    return state
+
+
 def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_precomp, shs, scales, rotations,
-                       cov3D_precomp, want_color_grad: bool = True, grad_depth=None, grad_alpha=None):
+                       cov3D_precomp, want_color_grad: bool = True, grad_depth=None, grad_alpha=None, camera_grads=None):
     """K7..K9.  Returns (dmeans3D, dmeans2D, dcolors, dopacity[P,1], dscales, drotations, dcov3D, dsh).
     ``want_color_grad=False`` (precomputed colours that need no gradient): dcolors is None and the blend backward keeps six sums
     per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (the depth build, its larger
-    scratch); ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient.  Both None is exactly gsr_backward."""
+    scratch); ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient.  Both None is exactly gsr_backward.
+    ``camera_grads`` (True or four flags for bg, viewmatrix, projmatrix, campos): gsr_backward_cam, and a ninth
+    element (d_bg[3], d_viewmatrix[16], d_projmatrix[16], d_campos[3]) -- flat, in the settings tensors' logical order, None where not
+    wanted.  None: eight elements, exactly the call without it."""
     lib = load_library()
     dev = means3D.device
     P, D = state.P, state.num_rendered
+    if camera_grads is not None:
+        want = _camera_want(camera_grads)
+        with _on(dev):
+            rec, cam_out = _camera_outputs(want, dev)
+            cam_scratch = torch.empty((lib.gsr_camera_scratch_bytes(1, P, state.H, state.W),), dtype=torch.uint8, device=dev)
+        if P == 0:     # nothing blended: dL/dbg = the sum of dL/dC, the rest 0
+            with _on(dev):
+                g = grad_color.to(dtype=torch.float32, device=dev).contiguous()
+                _check(lib.gsr_backward_cam(C.byref(state.settings), 0, 0, *([None] * 10), _ptr(g), *([None] * 11), C.byref(rec),
+                                            _ptr(cam_scratch), _stream(dev)), "gsr_backward_cam")
+            return (None,) * 8 + (cam_out,)
     M = 0 if shs is None else int(shs.shape[1])
     f32 = dict(dtype=torch.float32, device=dev)
     with _on(dev):
@@ -397,11 +451,14 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
         d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
         sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
         scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
-        _check(lib.gsr_backward_ext(C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations),
-                                    _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom),
-                                    _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch), _ptr(d_means3D),
-                                    _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot),
-                                    _ptr(d_cov), _ptr(d_sh), _ptr(gd), _ptr(ga), _stream(dev)), "gsr_backward_ext")
+        args = (C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(colors_precomp), _ptr(shs),
+                _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom), _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch),
+                _ptr(d_means3D), _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), _ptr(d_sh),
+                _ptr(gd), _ptr(ga))
+        if camera_grads is not None:
+            _check(lib.gsr_backward_cam(*args, C.byref(rec), _ptr(cam_scratch), _stream(dev)), "gsr_backward_cam")
+            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh, cam_out
+        _check(lib.gsr_backward_ext(*args, _stream(dev)), "gsr_backward_ext")
     return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
 
 
@@ -713,17 +770,20 @@ def _view_images(images, states, name, f32):
 
 
 def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp, shs, scales, rotations, cov3D_precomp,
-                             want_color_grad: bool = True, grad_out=None, grad_depth=None, grad_alpha=None):
+                             want_color_grad: bool = True, grad_out=None, grad_depth=None, grad_alpha=None, camera_grads=None):
     """Backward of all views.  Returns gradients already SUMMED over views (dmeans3D[P,3], dcolors, dopacity[P,1],
     dscales, drotations, dcov3D, dsh) plus the per-view means2D gradients [V,P,3].
     ``grad_depth`` ([V,1,H,W], or a sequence of V such images or None, or None): the depth images' gradient (views the forward fused
     into pairs are differentiated unfused; a None entry = no depth gradient for that view).
     ``grad_alpha`` (same forms): the rendered alphas' gradient (fused pairs stay fused; a None entry = no alpha gradient for that view).
-    None, or no image at all, for both is exactly gsr_backward_batch."""
+    None, or no image at all, for both is exactly gsr_backward_batch.
+    ``camera_grads`` (see rasterize_backward; the same flags for every view): gsr_backward_batch_cam (fused pairs run unfused), and an
+    eighth element, a list of V tuples (d_bg, d_viewmatrix, d_projmatrix, d_campos).  SH colours: the single-view path's."""
     lib = load_library()
     dev = means3D.device
     V = len(states)
     P = states[0].P
+    want = None if camera_grads is None else _camera_want(camera_grads)
     if states[0].forward_only:
         raise RuntimeError("rasterize_backward_batch: these states come from a forward_only forward (no record-slot offsets were produced)")
     f32 = dict(dtype=torch.float32, device=dev)
@@ -731,14 +791,16 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     ga = None if grad_alpha is None else _view_images(grad_alpha, states, "grad_alpha", f32)
     if shs is not None:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
         outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp,
-                                   grad_depth=None if gd is None else gd[v], grad_alpha=None if ga is None else ga[v])
+                                   grad_depth=None if gd is None else gd[v], grad_alpha=None if ga is None else ga[v],
+                                   **({} if want is None else {"camera_grads": want}))
                 for v in range(V)]
         sm = lambda k: None if outs[0][k] is None else torch.stack([o[k] for o in outs]).sum(0)  # noqa: E731
-        return sm(0), torch.stack([o[1] for o in outs]), None, sm(3), sm(4), sm(5), sm(6), sm(7)
+        res = (sm(0), torch.stack([o[1] for o in outs]), None, sm(3), sm(4), sm(5), sm(6), sm(7))
+        return res if want is None else res + ([o[8] for o in outs],)
     fused = states[0].raw_fused
-    if fused is not None and (gd is not None or ga is not None):
-        raise RuntimeError(f"rasterize_backward_batch: {'grad_depth' if gd is not None else 'grad_alpha'} is not supported with the fused "
-                           "raw-parameter activations")
+    if fused is not None and (gd is not None or ga is not None or want is not None):
+        raise RuntimeError(f"rasterize_backward_batch: {'grad_depth' if gd is not None else ('grad_alpha' if ga is not None else 'camera_grads')} "
+                           "is not supported with the fused raw-parameter activations")
     with _on(dev):
         g = grad_color.to(**f32).contiguous()
         sarr = (GsrSettings * V)()
@@ -770,12 +832,23 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             rawp = GsrRawParams(_ptr(fused[0]), None, None, _ptr(rotations), _ptr(states[0].act[1]), _ptr(scales),
                                 _ptr(d_rot), _ptr(d_opacity), _ptr(d_scales))
             rc = lib.gsr_backward_batch_raw(*args, None, None, None, _ptr(d_cov), C.byref(rawp), _stream(dev))
+        elif want is not None:     # camera gradients: one record per view, the camera pass behind the per-Gaussian backward
+            recs = (GsrCameraGrads * V)()
+            cam_out = []
+            for v in range(V):
+                recs[v], o = _camera_outputs(want, dev)
+                cam_out.append(o)
+            cam_scratch = torch.empty((lib.gsr_camera_scratch_bytes(V, P, states[0].H, states[0].W),), dtype=torch.uint8, device=dev)
+            rc = lib.gsr_backward_batch_cam(*args, _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
+                                            None if gd is None else _ptr_array(gd), None if ga is None else _ptr_array(ga), recs,
+                                            _ptr(cam_scratch), _stream(dev))
         else:
             rc = lib.gsr_backward_batch_ext(*args, _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
                                             None if gd is None else _ptr_array(gd), None if ga is None else _ptr_array(ga), _stream(dev))
         _check(rc, "gsr_backward_batch")
     # without a colour gradient, views that share a camera stay fused in the backward (one replay of the tile lists for both)
-    return d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None
+    res = (d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None)
+    return res if want is None else res + (cam_out,)
 
 
 def rigidity_forward(means3D, rotations, fg_idx, nbr, nw, nd, prev_inv, prev_off):

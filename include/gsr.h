@@ -186,6 +186,32 @@ int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, co
                      float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                      float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
                      const float* dL_dalpha, void* stream);
+/* Camera gradients (opt-in): dL/d(viewmatrix, projmatrix, campos, bg) of one view, fp32 device arrays of 16, 16, 3
+ * and 3 floats laid out like the gsr_settings members (the matrices column-major as stored).  A NULL member: that gradient is not wanted.
+ * viewmatrix[3, 7, 11, 15] and projmatrix[2, 6, 10, 14] are never read by the forward: their gradient is 0.  campos reaches the render
+ * only through the SH view direction: 0 for precomputed colours.  tanfovx / tanfovy are scalars of the settings, so no focal-length or
+ * field-of-view gradient is provided (J depends on them too). */
+typedef struct gsr_camera_grads {
+  float* dL_dviewmatrix;
+  float* dL_dprojmatrix;
+  float* dL_dcampos;
+  float* dL_dbg;
+} gsr_camera_grads;
+/* device scratch of the camera pass (one fp64 row per workgroup and view), for V views of P Gaussians and H x W pixels */
+size_t gsr_camera_scratch_bytes(int32_t V, int32_t P, int32_t H, int32_t W);
+/* gsr_backward_ext plus the camera gradients `cam` (host record of device pointers).  The camera pass runs behind the per-Gaussian
+ * backward on `stream`, over the same records: a second walk of each Gaussian's records with the fp64 chain, a reduction without atomics
+ * (bit-identical from run to run), and sum_pixels final_T dL/dC for bg.  `cam_scratch`: gsr_camera_scratch_bytes(1, P, H, W) bytes.
+ * Every other output is gsr_backward_ext's, bit for bit.  When the blend backward aborted (GSR_QUEUE_BWD_ERROR) the camera outputs are
+ * NaN, as dL_dmeans3D is.  P = 0: dL_dbg = sum of dL_dcolor, the rest 0 (geom / image state may then be NULL).
+ * cam == NULL: exactly gsr_backward_ext. */
+int gsr_backward_cam(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
+                     const float* dL_dalpha, const gsr_camera_grads* cam, void* cam_scratch, void* stream);
 /* The rendered alpha of V forwards of one image size, one launch: out_alpha[v * H * W + pix] = 1 - final_T of image_states[v] (device,
  * [V,H,W] contiguous), bit for bit the forward's own transmittance; 0 where nothing was blended.  Valid after any forward of those states
  * (single view, shared lists, batch, capacity mode, fused pairs, forward-only, depth cuts).  V in 1..GSR_MAX_BATCH. */
@@ -335,6 +361,18 @@ int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const ui
                            float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
                            const float* const* dL_dalpha_views, void* stream);
 
+/* gsr_backward_batch_ext plus the camera gradients of every view: cams[V] (host array of records, see gsr_camera_grads).  Views the forward
+ * fused into pairs are differentiated unfused (the camera pass needs each view's own records).  `cam_scratch`:
+ * gsr_camera_scratch_bytes(V, P, H, W) bytes.  Every other output is gsr_backward_batch_ext's for an unfused call.  cams == NULL: exactly
+ * gsr_backward_batch_ext. */
+int gsr_backward_batch_cam(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                           const float* scales, const float* rotations, const float* colors_precomp,
+                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                           void* const* binning_states, void* const* image_states, void* batch_state,
+                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
+                           const float* const* dL_dalpha_views, const gsr_camera_grads* cams, void* cam_scratch, void* stream);
 /* ---- neighbour terms of the t > 0 tracking loss, fused (caller side of the path):
  *   rigid, rot, iso of /root/reference/src/tracking/train_utils.py:198-222 as three means over (foreground point, neighbour).
  * All per-point arrays are indexed by foreground rank; fg_idx[n_fg] (int64) maps rank -> Gaussian; neighbor_* are [n_fg,K];
