@@ -465,12 +465,6 @@ int gsr_forward_capacity(const gsr_settings* s, int32_t P, const float* means3D,
                 nullptr, (hipStream_t)stream, late_count, gsr_rows_path_ok(cam.T) ? g.tile_rows : nullptr, (int)(flags & GSR_FORWARD_ONLY));
 }
 
-int gsr_forward_render_shared(const gsr_settings* s, int32_t P, uint32_t num_rendered, void* geom_state,
-                              void* owner_binning_state, const void* owner_image_state, void* image_state, float* out_color,
-                              float* out_depth, void* stream) {
-  return gsr_forward_render_shared_ex(s, P, num_rendered, geom_state, owner_binning_state, owner_image_state, image_state, out_color, out_depth,
-                                      0u, stream);
-}
 int gsr_forward_render_shared_ex(const gsr_settings* s, int32_t P, uint32_t num_rendered, void* geom_state, void* owner_binning_state,
                                  const void* owner_image_state, void* image_state, float* out_color, float* out_depth, uint32_t flags,
                                  void* stream) {
@@ -503,7 +497,7 @@ int gsr_forward_render_shared_ex(const gsr_settings* s, int32_t P, uint32_t num_
 }
 
 }  // extern "C"
-// The camera pass's table (gsr_backward_cam / gsr_backward_batch_cam)
+// The camera pass's table (the `cam` / `cams` member of the backward records)
 static void camera_header(GsrCamViews& cv, int V, int32_t P, const GsrCam& cam, const uint32_t* bwd_error, const float* means3D,
                           const float* scales, const float* rotations, const float* cov3D_precomp, const float* shs) {
   cv.V = V; cv.P = P; cv.nblk = gsr_camera_blocks(P, cam.H, cam.W); cv.sh_degree = cam.sh_degree; cv.M = cam.M;
@@ -524,24 +518,36 @@ extern "C" size_t gsr_camera_scratch_bytes(int32_t V, int32_t P, int32_t H, int3
   return gsr_align((size_t)(V > 0 ? V : 1) * (size_t)gsr_camera_blocks(P, H, W) * GSR_CAM_ROW * sizeof(double));
 }
 
-// gsr_backward, gsr_backward_depth, gsr_backward_ext and gsr_backward_cam: dL_ddepth == dL_dalpha == cg == nullptr is exactly gsr_backward
+static int check_batch(const char* who, int32_t V, const gsr_settings* s, const void* batch_state) {
+  if (V <= 0 || V > GSR_MAX_BATCH) { gsr_set_error("%s: V must be in 1..%d", who, GSR_MAX_BATCH); return -2; }
+  if (!s || !batch_state) { gsr_set_error("%s: NULL settings / batch_state", who); return -2; }
+  for (int v = 1; v < V; ++v)   // one preprocess launch (and one per-Gaussian backward) serves all views of a call
+    if ((s[v].prefiltered & GSR_SETTINGS_ANTIALIASING) != (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING)) {
+      gsr_set_error("%s: view %d's GSR_SETTINGS_ANTIALIASING differs from view 0's: all views of a call must agree", who, v);
+      return -2;
+    }
+  return 0;
+}
+
+// gsr_backward_ex; the all-NULL record is exactly gsr_backward
+static const gsr_backward_extras kNoExtras = {};
 static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                         const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
                         const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
                         const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                        const float* dL_dalpha, void* stream, const gsr_camera_grads* cg = nullptr, void* cam_scratch = nullptr) {
-  GsrRange _range(cg ? "gsr_backward_cam" : (dL_ddepth ? "gsr_backward_depth" : (dL_dalpha ? "gsr_backward_alpha" : "gsr_backward")));
+                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const gsr_backward_extras& ex,
+                        void* stream) {
+  GsrRange _range(ex.cam ? "gsr_backward_cam" : (ex.dL_ddepth ? "gsr_backward_depth" : (ex.dL_dalpha ? "gsr_backward_alpha" : "gsr_backward")));
   GsrCam cam;
   if (int rc = make_cam(s, &cam)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (cg && (!cam_scratch || !dL_dcolor)) { gsr_set_error("gsr_backward_cam: NULL cam_scratch / dL_dcolor"); return -2; }
+  if (ex.cam && (!ex.cam_scratch || !dL_dcolor)) { gsr_set_error("gsr_backward (camera gradients): NULL cam_scratch / dL_dcolor"); return -2; }
   if (P <= 0) {   // nothing blended: the image is the background (T = 1 everywhere), every other camera gradient is 0
-    if (!cg) return 0;
+    if (!ex.cam) return 0;
     GsrCamViews cv;
     camera_header(cv, 1, 0, cam, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    camera_view(cv.v[0], cam, *cg, (double*)cam_scratch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dL_dcolor);
+    camera_view(cv.v[0], cam, *ex.cam, (double*)ex.cam_scratch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, dL_dcolor);
     return gsr_launch_camera_bwd(cv, false, st);
   }
   if (!means3D || !radii || !geom_state || !image_state || !dL_dcolor || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity) {
@@ -555,16 +561,16 @@ static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered,
   gsr_carve_binning(const_cast<void*>(binning_state), num_rendered, &bs);
   float4* partials = (float4*)scratch;
   // depth: the per-entry dL/dz behind the records (scratch of gsr_backward_scratch_bytes_depth bytes); no entries, no depth term
-  float* dL_dz = (dL_ddepth && num_rendered > 0) ? (float*)((char*)scratch + gsr_depth_scratch_offset(num_rendered)) : nullptr;
+  float* dL_dz = (ex.dL_ddepth && num_rendered > 0) ? (float*)((char*)scratch + gsr_depth_scratch_offset(num_rendered)) : nullptr;
   if (num_rendered > 0) {
     GsrRenderViews rt;
     render_header(rt, 1, cam, im.tile_order, im.queue);
     rt.no_colour_grad = (!shs && !dL_dcolors) ? 1 : 0;   // precomputed colours and no gradient wanted for them
     rt.avg_list = num_rendered / (uint32_t)(cam.T > 0 ? cam.T : 1);
     fill_render_view(rt.v[0], cam, g, bs, im, nullptr, nullptr, dL_dcolor, partials);
-    rt.v[0].dL_dalpha = dL_dalpha;
+    rt.v[0].dL_dalpha = ex.dL_dalpha;
     GsrDepthViews dv;
-    if (dL_dz) { dv.dL_ddepth[0] = dL_ddepth; dv.dL_dz[0] = dL_dz; }
+    if (dL_dz) { dv.dL_ddepth[0] = ex.dL_ddepth; dv.dL_dz[0] = dL_dz; }
     if (int rc = gsr_launch_render_bwd(rt, st, dL_dz ? &dv : nullptr)) return rc;
   }
   const uint32_t* bwd_error = num_rendered > 0 ? im.queue + GSR_QUEUE_BWD_ERROR : nullptr;
@@ -572,68 +578,182 @@ static int backward_one(const gsr_settings* s, int32_t P, uint32_t num_rendered,
                                          partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales,
                                          dL_drotations, dL_dcov3D, dL_dsh, bwd_error, st, dL_dz))
     return rc;
-  if (!cg) return 0;
+  if (!ex.cam) return 0;
   GsrCamViews cv;   // the camera pass: the same records, behind the per-Gaussian backward on the same stream
   camera_header(cv, 1, P, cam, bwd_error, means3D, scales, rotations, cov3D_precomp, shs);
-  camera_view(cv.v[0], cam, *cg, (double*)cam_scratch, radii, &g, partials, dL_dz, im.final_T, g.clamped, num_rendered, dL_dcolor);
+  camera_view(cv.v[0], cam, *ex.cam, (double*)ex.cam_scratch, radii, &g, partials, dL_dz, im.final_T, g.clamped, num_rendered, dL_dcolor);
   return gsr_launch_camera_bwd(cv, cam.antialiasing != 0, st);
 }
-extern "C" {
-int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                 const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                 const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                 const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream) {
-  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
-                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, nullptr, nullptr, stream);
-}
-}  // extern "C"
+
+// gsr_backward_batch_ex; the all-NULL record (or tables whose entries are all nullptr) is exactly gsr_backward_batch
+static const gsr_backward_batch_extras kNoBatchExtras = {};
 static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                           const float* scales, const float* rotations, const float* colors_precomp,
                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
                           void* const* binning_states, void* const* image_states, void* batch_state,
                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                          float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw,
-                          const float* const* dL_ddepth_views, const float* const* dL_dalpha_views, void* stream,
-                          const gsr_camera_grads* cams = nullptr, void* cam_scratch = nullptr);
+                          float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_backward_batch_extras& ex,
+                          void* stream) {
+  GsrRange _range(ex.cams ? "gsr_backward_batch_cam" : (ex.dL_ddepth_views ? "gsr_backward_batch_depth"
+                                                                     : (ex.dL_dalpha_views ? "gsr_backward_batch_alpha" : "gsr_backward_batch")));
+  if (int rc = check_batch("gsr_backward_batch", V, s, batch_state)) return rc;
+  if (ex.cams && (!ex.cam_scratch || ex.raw)) { gsr_set_error("gsr_backward_batch (camera gradients): NULL cam_scratch, or raw parameters"); return -2; }
+  if (ex.raw && (ex.dL_ddepth_views || ex.dL_dalpha_views)) {   // the raw chain was never built with the depth / alpha terms
+    gsr_set_error("gsr_backward_batch (raw parameters): a depth / alpha gradient table cannot be combined with raw parameters");
+    return -2;
+  }
+  if (int rc = check_geometry_of(V, geometry_of)) return rc;
+  if (!num_rendered || !radii || !geom_states || !binning_states || !image_states || !dL_dcolor || !scratch ||
+      !dL_dmeans3D || !dL_dmeans2D || (!dL_dopacity && !ex.raw) || !means3D) {
+    gsr_set_error("gsr_backward_batch: NULL argument");
+    return -2;
+  }
+  if (ex.raw && (!ex.raw->unnorm_rotations || !ex.raw->d_unnorm_rotations || !ex.raw->d_logit_opacities || !ex.raw->d_log_scales || !scales || !rotations ||
+              !ex.raw->opacities_out || cov3D_precomp)) {
+    gsr_set_error("gsr_backward_batch (raw parameters): NULL pointer or cov3D_precomp given");
+    return -2;
+  }
+  if (P <= 0) {   // nothing blended: every view is its background (T = 1), every other camera gradient is 0
+    if (!ex.cams) return 0;
+    GsrCamViews cv;
+    GsrCam cam0;
+    if (int rc = make_cam(&s[0], &cam0)) return rc;
+    camera_header(cv, V, 0, cam0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    for (int v = 0; v < V; ++v) {
+      GsrCam cam;
+      if (int rc = make_cam(&s[v], &cam)) return rc;
+      camera_view(cv.v[v], cam, ex.cams[v], (double*)ex.cam_scratch + (size_t)v * cv.nblk * GSR_CAM_ROW, nullptr, nullptr, nullptr, nullptr,
+                  nullptr, nullptr, 0, dL_dcolor[v]);
+    }
+    return gsr_launch_camera_bwd(cv, false, (hipStream_t)stream);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  BatchState b;
+  gsr_carve_batch(batch_state, V, P, s[0].image_height, s[0].image_width, &b);
+  GsrBwdViews vw;
+  vw.V = V;
+  vw.bwd_error = nullptr;
+  vw.raw_rot = ex.raw ? ex.raw->unnorm_rotations : nullptr; vw.act_op = ex.raw ? ex.raw->opacities_out : nullptr; vw.act_sc = ex.raw ? scales : nullptr;
+  vw.d_raw_rot = ex.raw ? ex.raw->d_unnorm_rotations : nullptr; vw.d_raw_op = ex.raw ? ex.raw->d_logit_opacities : nullptr;
+  vw.d_raw_sc = ex.raw ? ex.raw->d_log_scales : nullptr;
+  GsrRenderViews rt;
+  GsrBinViews bt;          // only for a tile_order rebuild (ranges + flags)
+  bt.vlong_out = nullptr; bt.vlong_launch = 0;      // (set by gsr_launch_binning: the long-list hint of tile_sort)
+  bt.cut_lds = 0;
+  bool any = false;
+  // Pairs fused by the forward (pair_up) stay fused in the backward when no colour gradient is wanted (the pair pass carries
+  // none); otherwise every view takes its own pass over an LPT order rebuilt WITH the partners' tickets, and the fused order is
+  // put back afterwards (batch_state always holds the forward's order between calls: two tile_order launches on the rare path,
+  // none on the common one).
+  int partner[GSR_MAX_BATCH], fused[GSR_MAX_BATCH];
+  pair_up(V, geometry_of, num_rendered, partner, fused);
+  bool pairs_fwd = false;
+  for (int v = 0; v < V; ++v) pairs_fwd = pairs_fwd || fused[v];
+  bool depth = false;   // a depth gradient for some view: the depth build, which has no fused pairs (the call runs unfused)
+  for (int v = 0; ex.dL_ddepth_views && v < V; ++v) depth = depth || ex.dL_ddepth_views[v] != nullptr;
+  GsrDepthViews dv;
+  GsrAaViews av;          // anti-aliasing: every view's records (staged o'); check_batch made the views agree on the bit
+  const bool aa = (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING) != 0;
+  // (the camera pass needs each view's own records: camera gradients run unfused, as the depth build does)
+  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth && !ex.cams;
+  if (!fuse_bwd)
+    for (int v = 0; v < V; ++v) { partner[v] = -1; fused[v] = 0; }
+  for (int v = 0; v < V; ++v) {
+    GsrCam cam;
+    if (int rc = make_cam(&s[v], &cam)) return rc;
+    const int owner = geometry_of ? geometry_of[v] : v;
+    GeomState g; ImageState im, im_owner; BinningState bs;
+    gsr_carve_geom(geom_states[v], P, &g);
+    gsr_carve_image(image_states[v], cam.H, cam.W, &im);
+    gsr_carve_image(image_states[owner], cam.H, cam.W, &im_owner);
+    gsr_carve_binning(binning_states[owner], num_rendered[owner], &bs);
+    if (num_rendered[v] > 0 && (!binning_states[owner] || !scratch[v])) { gsr_set_error("gsr_backward_batch: NULL binning/scratch"); return -2; }
+    if (v == 0) { render_header(rt, V, cam, b.order, b.queue); rt.no_colour_grad = (!dL_dcolors && !dL_dcolors_views) ? 1 : 0; }
+    fill_render_view(rt.v[v], cam, g, bs, im, nullptr, nullptr, dL_dcolor[v], (float4*)scratch[v]);
+    rt.v[v].ranges = im_owner.ranges;
+    // alpha: one more per-pixel term of the blend backward, fused pairs included (each view of a pair brings its own image)
+    rt.v[v].dL_dalpha = ex.dL_dalpha_views ? ex.dL_dalpha_views[v] : nullptr;
+    rt.v[v].partner = partner[v]; rt.v[v].fused_alias = fused[v];
+    if (v == 0) { bt.V = V; bt.T = cam.T; bt.gx = cam.gx; bt.order = b.order; bt.queue = b.queue; bt.counts_out = nullptr; bt.P = P; bt.wave_cap = 512; bt.rows = 0; bt.forward_only = 0; }
+    bt.v[v].ranges = im_owner.ranges; bt.v[v].fused_alias = (uint32_t)fused[v]; bt.v[v].shares_lists = owner != v;
+    any = any || num_rendered[v] > 0;
+    GsrBwdView& w = vw.v[v];
+    w.view = cam.view; w.proj = cam.proj; w.radii = radii[v]; w.offsets = g.offsets;
+    w.used = g.used; w.tracked = g.counters + 1;
+    w.partials = (const float4*)scratch[v]; w.dL_dmeans2D = dL_dmeans2D[v];
+    w.dL_dcolors = dL_dcolors_views ? dL_dcolors_views[v] : nullptr;
+    w.partner_dL_dmeans2D = partner[v] >= 0 ? dL_dmeans2D[partner[v]] : nullptr;
+    w.fused_alias = fused[v];
+    w.cap = num_rendered[v];
+    w.W = cam.W; w.H = cam.H; w.tanfovx = cam.tanfovx; w.tanfovy = cam.tanfovy;
+    av.rec[v] = g.rec;
+    if (depth) {   // every view's scratch holds gsr_backward_scratch_bytes_depth(P, num_rendered[v]): the blend writes dL/dz for all of them
+      dv.dL_ddepth[v] = ex.dL_ddepth_views[v];
+      dv.dL_dz[v] = num_rendered[v] > 0 ? (float*)((char*)scratch[v] + gsr_depth_scratch_offset(num_rendered[v])) : nullptr;
+    }
+  }
+  GsrDepthViews dvp = dv;   // the per-Gaussian backward: only views with a depth gradient add the depth term
+  for (int v = 0; depth && v < V; ++v) if (!dv.dL_ddepth[v]) dvp.dL_dz[v] = nullptr;
+  if (any) {
+    { uint64_t tot = 0; for (int v = 0; v < V; ++v) tot += num_rendered[v]; rt.avg_list = (uint32_t)(tot / ((uint64_t)V * (uint64_t)(rt.T > 0 ? rt.T : 1))); }
+    const bool rebuild = pairs_fwd && !fuse_bwd;
+    if (rebuild)
+      if (int rc = gsr_launch_tile_order(bt, st)) return rc;
+    if (int rc = gsr_launch_render_bwd(rt, st, depth ? &dv : nullptr)) return rc;
+    vw.bwd_error = rt.queue + GSR_QUEUE_BWD_ERROR;
+    if (rebuild) {
+      pair_up(V, geometry_of, num_rendered, partner, fused);
+      for (int v = 0; v < V; ++v) bt.v[v].fused_alias = (uint32_t)fused[v];
+      if (int rc = gsr_launch_tile_order(bt, st)) return rc;
+    }
+  }
+  (void)colors_precomp;
+  if (int rc = gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
+                                               dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st,
+                                               (depth && any) ? &dvp : nullptr, aa ? &av : nullptr))
+    return rc;
+  if (!ex.cams) return 0;
+  // the camera pass: one launch for every view (blockIdx.y), each view's own records (the call ran unfused)
+  GsrCamViews cv;
+  GsrCam cam0;
+  if (int rc = make_cam(&s[0], &cam0)) return rc;
+  camera_header(cv, V, P, cam0, vw.bwd_error, means3D, scales, rotations, cov3D_precomp, nullptr);
+  double* slab = (double*)ex.cam_scratch;
+  for (int v = 0; v < V; ++v) {
+    GsrCam cam;
+    if (int rc = make_cam(&s[v], &cam)) return rc;
+    GeomState g; ImageState im;
+    gsr_carve_geom(geom_states[v], P, &g);
+    gsr_carve_image(image_states[v], cam.H, cam.W, &im);
+    camera_view(cv.v[v], cam, ex.cams[v], slab + (size_t)v * cv.nblk * GSR_CAM_ROW, radii[v], &g, vw.v[v].partials,
+                depth ? dvp.dL_dz[v] : nullptr, im.final_T, nullptr, num_rendered[v], dL_dcolor[v]);
+  }
+  return gsr_launch_camera_bwd(cv, aa, st);
+}
+
 extern "C" {
-int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                       const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                       const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                       const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                       float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream) {
+int gsr_backward_ex(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                    const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                    const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                    const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                    float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                    float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const gsr_backward_extras* ex,
+                    void* stream) {
   return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
                       image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, dL_ddepth, nullptr, stream);
+                      dL_dcov3D, dL_dsh, ex ? *ex : kNoExtras, stream);
 }
-int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                     const float* dL_dalpha, void* stream) {
-  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
-                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, dL_ddepth, dL_dalpha, stream);
+int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                 const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                 const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                 const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream) {
+  return gsr_backward_ex(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
+                         image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                         dL_dcov3D, dL_dsh, nullptr, stream);
 }
-
-int gsr_backward_cam(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                     const float* dL_dalpha, const gsr_camera_grads* cam, void* cam_scratch, void* stream) {
-  return backward_one(s, P, num_rendered, means3D, scales, rotations, colors_precomp, shs, cov3D_precomp, radii, geom_state, binning_state,
-                      image_state, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                      dL_dcov3D, dL_dsh, dL_ddepth, dL_dalpha, stream, cam, cam_scratch);
-}
-
 int gsr_alpha_views(int32_t V, int32_t H, int32_t W, void* const* image_states, float* out_alpha, void* stream) {
   GsrRange _range("gsr_alpha_views");
   if (V <= 0 || V > GSR_MAX_BATCH || H <= 0 || W <= 0) { gsr_set_error("gsr_alpha_views: V must be in 1..%d and H, W positive", GSR_MAX_BATCH); return -2; }
@@ -658,16 +778,6 @@ int gsr_alpha_views(int32_t V, int32_t H, int32_t W, void* const* image_states, 
 // the caller keeps it from the forward to the backward like the other state buffers.
 size_t gsr_batch_state_bytes(int32_t V, int32_t P, int32_t H, int32_t W) { BatchState b; return gsr_carve_batch(nullptr, V, P, H, W, &b); }
 
-static int check_batch(const char* who, int32_t V, const gsr_settings* s, const void* batch_state) {
-  if (V <= 0 || V > GSR_MAX_BATCH) { gsr_set_error("%s: V must be in 1..%d", who, GSR_MAX_BATCH); return -2; }
-  if (!s || !batch_state) { gsr_set_error("%s: NULL settings / batch_state", who); return -2; }
-  for (int v = 1; v < V; ++v)   // one preprocess launch (and one per-Gaussian backward) serves all views of a call
-    if ((s[v].prefiltered & GSR_SETTINGS_ANTIALIASING) != (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING)) {
-      gsr_set_error("%s: view %d's GSR_SETTINGS_ANTIALIASING differs from view 0's: all views of a call must agree", who, v);
-      return -2;
-    }
-  return 0;
-}
 
 int gsr_arm_depth_cuts(int32_t V, const uint32_t* const* cut_in, uint32_t* const* cut_out, uint32_t* redo_flags, float margin) {
   if (V == 0) { t_cuts.V = 0; return 0; }      // disarm (a caller whose forward failed before it got to the binning)
@@ -746,18 +856,6 @@ int gsr_forward_batch(int32_t V, const gsr_settings* s, int32_t P, const float* 
                 b.queue, geometry_of, (hipStream_t)stream, nullptr, b.tile_rows, flags, colors_views);
 }
 
-int gsr_forward_batch_capacity(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* scales,
-                               const float* rotations, const float* opacities, const float* colors_precomp,
-                               const float* const* colors_views, const float* shs, const float* cov3D_precomp,
-                               void* const* geom_states, int32_t* const* radii, void* const* binning_states,
-                               const uint32_t* capacity_entries, void* const* image_states, void* batch_state,
-                               const int32_t* geometry_of, float* const* out_color, float* const* out_depth,
-                               uint32_t* counts_dev, void* stream) {
-  return gsr_forward_batch_capacity_raw(V, s, P, means3D, scales, rotations, opacities, colors_precomp, colors_views, shs, cov3D_precomp,
-                                        geom_states, radii, binning_states, capacity_entries, image_states, batch_state, geometry_of,
-                                        out_color, out_depth, counts_dev, nullptr, stream);
-}
-
 int gsr_forward_batch_capacity_raw(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* scales,
                                    const float* rotations, const float* opacities, const float* colors_precomp,
                                    const float* const* colors_views, const float* shs, const float* cov3D_precomp,
@@ -787,218 +885,29 @@ int gsr_forward_batch_capacity_raw(int32_t V, const gsr_settings* s, int32_t P, 
                 b.queue, geometry_of, (hipStream_t)stream, counts_dev, b.tile_rows);
 }
 
+int gsr_backward_batch_ex(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                          const float* scales, const float* rotations, const float* colors_precomp,
+                          const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                          void* const* binning_states, void* const* image_states, void* batch_state,
+                          const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                          float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                          float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_backward_batch_extras* ex,
+                          void* stream) {
+  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, ex ? *ex : kNoBatchExtras, stream);
+}
 int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp,
                        const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
                        void* const* binning_states, void* const* image_states, void* batch_state,
                        const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                       float* const* dL_dmeans2D,
-                       float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
-                       float* dL_drotations, float* dL_dcov3D, void* stream) {
-  return gsr_backward_batch_raw(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
-                                binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                                dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, stream);
+                       float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                       float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* stream) {
+  return gsr_backward_batch_ex(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
+                               binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D,
+                               dL_dcolors, dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, stream);
 }
-
-int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                             const float* scales, const float* rotations, const float* colors_precomp,
-                             const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                             void* const* binning_states, void* const* image_states, void* batch_state,
-                             const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                             float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                             void* stream) {
-  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
-                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, nullptr, stream);
-}
-
-int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                           const float* scales, const float* rotations, const float* colors_precomp,
-                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                           void* const* binning_states, void* const* image_states, void* batch_state,
-                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                           const float* const* dL_dalpha_views, void* stream) {
-  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
-                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, dL_dalpha_views,
-                        stream);
-}
-
-int gsr_backward_batch_cam(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                           const float* scales, const float* rotations, const float* colors_precomp,
-                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                           void* const* binning_states, void* const* image_states, void* batch_state,
-                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                           const float* const* dL_dalpha_views, const gsr_camera_grads* cams, void* cam_scratch, void* stream) {
-  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
-                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, dL_ddepth_views, dL_dalpha_views,
-                        stream, cams, cam_scratch);
-}
-
-int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                       const float* scales, const float* rotations, const float* colors_precomp,
-                       const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                       void* const* binning_states, void* const* image_states, void* batch_state,
-                       const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                       float* const* dL_dmeans2D,
-                       float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
-                       float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, void* stream) {
-  return backward_batch(V, s, P, num_rendered, means3D, scales, rotations, colors_precomp, cov3D_precomp, radii, geom_states,
-                        binning_states, image_states, batch_state, geometry_of, dL_dcolor, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
-                        dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, raw, nullptr, nullptr, stream);
-}
-}  // extern "C"
-
-// gsr_backward_batch_raw, gsr_backward_batch_depth and gsr_backward_batch_ext: dL_ddepth_views and dL_dalpha_views == nullptr (or all of
-// their entries nullptr) is exactly the first
-static int backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                       const float* scales, const float* rotations, const float* colors_precomp,
-                       const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                       void* const* binning_states, void* const* image_states, void* batch_state,
-                       const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                       float* const* dL_dmeans2D,
-                       float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity, float* dL_dscales,
-                       float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, const float* const* dL_ddepth_views,
-                       const float* const* dL_dalpha_views, void* stream, const gsr_camera_grads* cams, void* cam_scratch) {
-  GsrRange _range(cams ? "gsr_backward_batch_cam" : (dL_ddepth_views ? "gsr_backward_batch_depth"
-                                                                     : (dL_dalpha_views ? "gsr_backward_batch_alpha" : "gsr_backward_batch")));
-  if (int rc = check_batch("gsr_backward_batch", V, s, batch_state)) return rc;
-  if (cams && (!cam_scratch || raw)) { gsr_set_error("gsr_backward_batch_cam: NULL cam_scratch, or raw parameters"); return -2; }
-  if (int rc = check_geometry_of(V, geometry_of)) return rc;
-  if (!num_rendered || !radii || !geom_states || !binning_states || !image_states || !dL_dcolor || !scratch ||
-      !dL_dmeans3D || !dL_dmeans2D || (!dL_dopacity && !raw) || !means3D) {
-    gsr_set_error("gsr_backward_batch: NULL argument");
-    return -2;
-  }
-  if (raw && (!raw->unnorm_rotations || !raw->d_unnorm_rotations || !raw->d_logit_opacities || !raw->d_log_scales || !scales || !rotations ||
-              !raw->opacities_out || cov3D_precomp)) {
-    gsr_set_error("gsr_backward_batch (raw parameters): NULL pointer or cov3D_precomp given");
-    return -2;
-  }
-  if (P <= 0) {   // nothing blended: every view is its background (T = 1), every other camera gradient is 0
-    if (!cams) return 0;
-    GsrCamViews cv;
-    GsrCam cam0;
-    if (int rc = make_cam(&s[0], &cam0)) return rc;
-    camera_header(cv, V, 0, cam0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    for (int v = 0; v < V; ++v) {
-      GsrCam cam;
-      if (int rc = make_cam(&s[v], &cam)) return rc;
-      camera_view(cv.v[v], cam, cams[v], (double*)cam_scratch + (size_t)v * cv.nblk * GSR_CAM_ROW, nullptr, nullptr, nullptr, nullptr,
-                  nullptr, nullptr, 0, dL_dcolor[v]);
-    }
-    return gsr_launch_camera_bwd(cv, false, (hipStream_t)stream);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  BatchState b;
-  gsr_carve_batch(batch_state, V, P, s[0].image_height, s[0].image_width, &b);
-  GsrBwdViews vw;
-  vw.V = V;
-  vw.bwd_error = nullptr;
-  vw.raw_rot = raw ? raw->unnorm_rotations : nullptr; vw.act_op = raw ? raw->opacities_out : nullptr; vw.act_sc = raw ? scales : nullptr;
-  vw.d_raw_rot = raw ? raw->d_unnorm_rotations : nullptr; vw.d_raw_op = raw ? raw->d_logit_opacities : nullptr;
-  vw.d_raw_sc = raw ? raw->d_log_scales : nullptr;
-  GsrRenderViews rt;
-  GsrBinViews bt;          // only for a tile_order rebuild (ranges + flags)
-  bt.vlong_out = nullptr; bt.vlong_launch = 0;      // (set by gsr_launch_binning: the long-list hint of tile_sort)
-  bt.cut_lds = 0;
-  bool any = false;
-  // Pairs fused by the forward (pair_up) stay fused in the backward when no colour gradient is wanted (the pair pass carries
-  // none); otherwise every view takes its own pass over an LPT order rebuilt WITH the partners' tickets, and the fused order is
-  // put back afterwards (batch_state always holds the forward's order between calls: two tile_order launches on the rare path,
-  // none on the common one).
-  int partner[GSR_MAX_BATCH], fused[GSR_MAX_BATCH];
-  pair_up(V, geometry_of, num_rendered, partner, fused);
-  bool pairs_fwd = false;
-  for (int v = 0; v < V; ++v) pairs_fwd = pairs_fwd || fused[v];
-  bool depth = false;   // a depth gradient for some view: the depth build, which has no fused pairs (the call runs unfused)
-  for (int v = 0; dL_ddepth_views && v < V; ++v) depth = depth || dL_ddepth_views[v] != nullptr;
-  GsrDepthViews dv;
-  GsrAaViews av;          // anti-aliasing: every view's records (staged o'); check_batch made the views agree on the bit
-  const bool aa = (s[0].prefiltered & GSR_SETTINGS_ANTIALIASING) != 0;
-  // (the camera pass needs each view's own records: camera gradients run unfused, as the depth build does)
-  const bool fuse_bwd = pairs_fwd && !dL_dcolors && !dL_dcolors_views && !depth && !cams;
-  if (!fuse_bwd)
-    for (int v = 0; v < V; ++v) { partner[v] = -1; fused[v] = 0; }
-  for (int v = 0; v < V; ++v) {
-    GsrCam cam;
-    if (int rc = make_cam(&s[v], &cam)) return rc;
-    const int owner = geometry_of ? geometry_of[v] : v;
-    GeomState g; ImageState im, im_owner; BinningState bs;
-    gsr_carve_geom(geom_states[v], P, &g);
-    gsr_carve_image(image_states[v], cam.H, cam.W, &im);
-    gsr_carve_image(image_states[owner], cam.H, cam.W, &im_owner);
-    gsr_carve_binning(binning_states[owner], num_rendered[owner], &bs);
-    if (num_rendered[v] > 0 && (!binning_states[owner] || !scratch[v])) { gsr_set_error("gsr_backward_batch: NULL binning/scratch"); return -2; }
-    if (v == 0) { render_header(rt, V, cam, b.order, b.queue); rt.no_colour_grad = (!dL_dcolors && !dL_dcolors_views) ? 1 : 0; }
-    fill_render_view(rt.v[v], cam, g, bs, im, nullptr, nullptr, dL_dcolor[v], (float4*)scratch[v]);
-    rt.v[v].ranges = im_owner.ranges;
-    // alpha: one more per-pixel term of the blend backward, fused pairs included (each view of a pair brings its own image)
-    rt.v[v].dL_dalpha = dL_dalpha_views ? dL_dalpha_views[v] : nullptr;
-    rt.v[v].partner = partner[v]; rt.v[v].fused_alias = fused[v];
-    if (v == 0) { bt.V = V; bt.T = cam.T; bt.gx = cam.gx; bt.order = b.order; bt.queue = b.queue; bt.counts_out = nullptr; bt.P = P; bt.wave_cap = 512; bt.rows = 0; bt.forward_only = 0; }
-    bt.v[v].ranges = im_owner.ranges; bt.v[v].fused_alias = (uint32_t)fused[v]; bt.v[v].shares_lists = owner != v;
-    any = any || num_rendered[v] > 0;
-    GsrBwdView& w = vw.v[v];
-    w.view = cam.view; w.proj = cam.proj; w.radii = radii[v]; w.offsets = g.offsets;
-    w.used = g.used; w.tracked = g.counters + 1;
-    w.partials = (const float4*)scratch[v]; w.dL_dmeans2D = dL_dmeans2D[v];
-    w.dL_dcolors = dL_dcolors_views ? dL_dcolors_views[v] : nullptr;
-    w.partner_dL_dmeans2D = partner[v] >= 0 ? dL_dmeans2D[partner[v]] : nullptr;
-    w.fused_alias = fused[v];
-    w.cap = num_rendered[v];
-    w.W = cam.W; w.H = cam.H; w.tanfovx = cam.tanfovx; w.tanfovy = cam.tanfovy;
-    av.rec[v] = g.rec;
-    if (depth) {   // every view's scratch holds gsr_backward_scratch_bytes_depth(P, num_rendered[v]): the blend writes dL/dz for all of them
-      dv.dL_ddepth[v] = dL_ddepth_views[v];
-      dv.dL_dz[v] = num_rendered[v] > 0 ? (float*)((char*)scratch[v] + gsr_depth_scratch_offset(num_rendered[v])) : nullptr;
-    }
-  }
-  GsrDepthViews dvp = dv;   // the per-Gaussian backward: only views with a depth gradient add the depth term
-  for (int v = 0; depth && v < V; ++v) if (!dv.dL_ddepth[v]) dvp.dL_dz[v] = nullptr;
-  if (any) {
-    { uint64_t tot = 0; for (int v = 0; v < V; ++v) tot += num_rendered[v]; rt.avg_list = (uint32_t)(tot / ((uint64_t)V * (uint64_t)(rt.T > 0 ? rt.T : 1))); }
-    const bool rebuild = pairs_fwd && !fuse_bwd;
-    if (rebuild)
-      if (int rc = gsr_launch_tile_order(bt, st)) return rc;
-    if (int rc = gsr_launch_render_bwd(rt, st, depth ? &dv : nullptr)) return rc;
-    vw.bwd_error = rt.queue + GSR_QUEUE_BWD_ERROR;
-    if (rebuild) {
-      pair_up(V, geometry_of, num_rendered, partner, fused);
-      for (int v = 0; v < V; ++v) bt.v[v].fused_alias = (uint32_t)fused[v];
-      if (int rc = gsr_launch_tile_order(bt, st)) return rc;
-    }
-  }
-  (void)colors_precomp;
-  if (int rc = gsr_launch_preprocess_bwd_views(vw, P, s[0].scale_modifier, means3D, scales, rotations, cov3D_precomp, dL_dmeans3D,
-                                               dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, st,
-                                               (depth && any) ? &dvp : nullptr, aa ? &av : nullptr))
-    return rc;
-  if (!cams) return 0;
-  // the camera pass: one launch for every view (blockIdx.y), each view's own records (the call ran unfused)
-  GsrCamViews cv;
-  GsrCam cam0;
-  if (int rc = make_cam(&s[0], &cam0)) return rc;
-  camera_header(cv, V, P, cam0, vw.bwd_error, means3D, scales, rotations, cov3D_precomp, nullptr);
-  double* slab = (double*)cam_scratch;
-  for (int v = 0; v < V; ++v) {
-    GsrCam cam;
-    if (int rc = make_cam(&s[v], &cam)) return rc;
-    GeomState g; ImageState im;
-    gsr_carve_geom(geom_states[v], P, &g);
-    gsr_carve_image(image_states[v], cam.H, cam.W, &im);
-    camera_view(cv.v[v], cam, cams[v], slab + (size_t)v * cv.nblk * GSR_CAM_ROW, radii[v], &g, vw.v[v].partials,
-                depth ? dvp.dL_dz[v] : nullptr, im.final_T, nullptr, num_rendered[v], dL_dcolor[v]);
-  }
-  return gsr_launch_camera_bwd(cv, aa, st);
-}
-extern "C" {
 
 int32_t gsr_rigidity_blocks(int32_t n_fg) { return gsr_rigidity_fwd_blocks(n_fg); }
 

@@ -65,7 +65,7 @@ Settings make_settings(const torch::Tensor& bg, const torch::Tensor& viewmatrix,
   return o;
 }
 
-// Tile-list reuse (include/gsr.h: gsr_forward_preprocess_same / gsr_forward_render_shared).  The reference renders every camera twice with
+// Tile-list reuse (include/gsr.h: gsr_forward_preprocess_same / gsr_forward_render_shared_ex).  The reference renders every camera twice with
 // the same geometry and other colours -- get_loss: colours then segmentation colours (/root/reference/src/tracking/train_utils.py:178,192),
 // predict.py: colours then an all-ones mask (:115-123) -- through two separate GaussianRasterizer calls whose geometry tensors are fresh
 // copies.  The layer remembers the LAST forward's states (geometry + binning + image tensors); the next forward of the same (P, H, W,
@@ -234,7 +234,7 @@ Forward rasterize_forward(const torch::Tensor& background, const torch::Tensor& 
   if (candidate && same && D > 0 && lc.D == D) {
     // same geometry, same camera as the previous forward (compared on the device, bit for bit): its lists are this render's lists
     check(gsr_forward_render_shared_ex(&st.s, (int32_t)P, lc.layout, geom.data_ptr(), lc.binning.data_ptr(), lc.image.data_ptr(), image.data_ptr(),
-                                       color.data_ptr<float>(), depth.data_ptr<float>(), fwd_flags, stream), "gsr_forward_render_shared");
+                                       color.data_ptr<float>(), depth.data_ptr<float>(), fwd_flags, stream), "gsr_forward_render_shared_ex");
     ++S->reuse_hits;
     S->note_twin(true);
     return finish(D, lc.layout, lc.binning);
@@ -292,6 +292,7 @@ backward_body(const torch::Tensor& background, const torch::Tensor& means3D, con
   auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
   const bool cam_on = camg && (camg->want[0] || camg->want[1] || camg->want[2] || camg->want[3]);
   gsr_camera_grads cg = {nullptr, nullptr, nullptr, nullptr};
+  gsr_backward_extras ex = {nullptr, nullptr, nullptr, nullptr};   // filled below: camera record, then the depth / alpha gradients
   torch::Tensor cam_scratch;
   if (cam_on) {
     static const int64_t n[4] = {3, 16, 16, 3};
@@ -303,6 +304,7 @@ backward_body(const torch::Tensor& background, const torch::Tensor& means3D, con
     cg.dL_dcampos = camg->want[3] ? camg->out[3].data_ptr<float>() : nullptr;
     cam_scratch = torch::empty({(int64_t)gsr_camera_scratch_bytes(1, (int32_t)P, (int32_t)H, (int32_t)W)},
                                torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    ex.cam = &cg; ex.cam_scratch = cam_scratch.data_ptr();
   }
   torch::Tensor d_means3D = torch::empty({P, 3}, f32), d_means2D = torch::empty({P, 3}, f32), d_opacity = torch::empty({P, 1}, f32);
   torch::Tensor d_colors = (M || !want_color_grad) ? torch::empty({0}, f32) : torch::empty({P, 3}, f32);
@@ -316,10 +318,10 @@ backward_body(const torch::Tensor& background, const torch::Tensor& means3D, con
       Settings st = make_settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier, degree, M, false, dev,
                                   antialiasing);
       const torch::Tensor g = f32c(dL_dout_color, dev);
-      check(gsr_backward_cam(&st.s, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             g.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, &cg, cam_scratch.data_ptr(), (void*)c10::hip::getCurrentHIPStream(dev.index()).stream()),
-            "gsr_backward_cam");
+      check(gsr_backward_ex(&st.s, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            g.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ex,
+                            (void*)c10::hip::getCurrentHIPStream(dev.index()).stream()),
+            "gsr_backward_ex");
     }
     return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
   }
@@ -349,22 +351,14 @@ backward_body(const torch::Tensor& background, const torch::Tensor& means3D, con
   torch::Tensor scratch = torch::empty({(int64_t)(has_depth ? gsr_backward_scratch_bytes_depth((int32_t)P, (uint32_t)R)
                                                              : gsr_backward_scratch_bytes((int32_t)P, (uint32_t)R))},
                                        torch::TensorOptions().dtype(torch::kUInt8).device(dev));
-  // camera gradients: gsr_backward_cam (gsr_backward_ext plus the camera pass); without them, gsr_backward_ext as before
-  if (cam_on)
-    check(gsr_backward_cam(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
-                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
-                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
-                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
-                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, &cg,
-                           cam_scratch.data_ptr(), stream),
-          "gsr_backward_cam");
-  else
-    check(gsr_backward_ext(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
-                           radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
-                           g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
-                           optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh),
-                           has_depth ? gd.data_ptr<float>() : nullptr, has_alpha ? ga.data_ptr<float>() : nullptr, stream),
-          "gsr_backward_ext");
+  ex.dL_ddepth = has_depth ? gd.data_ptr<float>() : nullptr;
+  ex.dL_dalpha = has_alpha ? ga.data_ptr<float>() : nullptr;
+  check(gsr_backward_ex(&st.s, (int32_t)P, (uint32_t)R, fptr(m3), fptr(sc), fptr(rot), fptr(col), fptr(shs), fptr(cov),
+                        radii.data_ptr<int32_t>(), geomBuffer.data_ptr(), R ? binningBuffer.data_ptr() : nullptr, imageBuffer.data_ptr(),
+                        g.data_ptr<float>(), R ? scratch.data_ptr() : nullptr, d_means3D.data_ptr<float>(), d_means2D.data_ptr<float>(),
+                        optr(d_colors), d_opacity.data_ptr<float>(), optr(d_scales), optr(d_rot), d_cov.data_ptr<float>(), optr(d_sh), &ex,
+                        stream),
+        "gsr_backward_ex");
   return std::make_tuple(d_means2D, d_colors, d_opacity, d_means3D, d_cov, d_sh, d_scales, d_rot);
 }
 
@@ -388,7 +382,7 @@ rasterize_gaussians_backward(const torch::Tensor& background, const torch::Tenso
 // (profiles/r04_dropin_host_profile.txt); here the whole call is ONE crossing: GaussianRasterizer.forward -> _C.rasterize -> this node.
 // Inputs in the order of upstream's Python _RasterizeGaussians.apply (means3D, means2D, sh, colors_precomp, opacities, scales,
 // rotations, cov3Ds_precomp) followed by the settings record's fields; outputs (color, radii, depth), and alpha = 1 - final_T [1, H, W]
-// when return_alpha (one gsr_alpha_views launch behind the forward; differentiable through gsr_backward_ext).  means2D is the gradient holder
+// when return_alpha (one gsr_alpha_views launch behind the forward; differentiable through gsr_backward_ex).  means2D is the gradient holder
 // the reference reads back (`rendervar['means2D'].grad`, /root/reference/src/tracking/external.py:139-140): its values are ignored.
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
   static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor means3D, torch::Tensor means2D,
@@ -450,7 +444,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     // grads[2] (depth): ignored unless the call opted in (differentiable_depth); then the depth build -- when autograd delivers one
     c10::optional<torch::Tensor> gd;
     if (ctx->saved_data["depth"].toBool() && grads[2].defined()) gd = grads[2];
-    // grads[3] (alpha, when the call returned it): always differentiable -- when autograd delivers one, gsr_backward_ext adds its term
+    // grads[3] (alpha, when the call returned it): always differentiable -- when autograd delivers one, gsr_backward_ex adds its term
     c10::optional<torch::Tensor> ga;
     if (grads.size() > 3 && grads[3].defined()) ga = grads[3];
     if (!g.defined()) g = torch::zeros({3, H, W}, m3.options().dtype(torch::kFloat32));

@@ -69,14 +69,23 @@ class GsrCameraGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dL_dviewmatrix", "dL_dprojmatrix", "dL_dcampos", "dL_dbg")]
 
 
+class GsrBackwardExtras(C.Structure):
+    """gsr_backward_extras of include/gsr.h: the opt-in parts of gsr_backward_ex; all NULL is the plain backward."""
+    _fields_ = [(n, C.c_void_p) for n in ("dL_ddepth", "dL_dalpha", "cam", "cam_scratch")]
+
+
+class GsrBackwardBatchExtras(C.Structure):
+    """gsr_backward_batch_extras of include/gsr.h: the opt-in parts of gsr_backward_batch_ex; all NULL is the plain batch backward."""
+    _fields_ = [(n, C.c_void_p) for n in ("raw", "dL_ddepth_views", "dL_dalpha_views", "cams", "cam_scratch")]
+
+
 EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes", "gsr_binning_bytes",
            "gsr_backward_scratch_bytes", "gsr_forward_preprocess", "gsr_forward_render", "gsr_backward",
-           "gsr_forward_preprocess_same", "gsr_forward_render_shared", "gsr_forward_render_ex", "gsr_forward_render_shared_ex", "gsr_forward_capacity", "gsr_wait_block_counts",
+           "gsr_forward_preprocess_same", "gsr_backward_ex", "gsr_forward_render_ex", "gsr_forward_render_shared_ex", "gsr_forward_capacity", "gsr_wait_block_counts",
            "gsr_mark_visible", "gsr_debug_get_views", "gsr_selftest", "gsr_profile_begin", "gsr_profile_end",
            "gsr_batch_state_bytes", "gsr_forward_preprocess_batch", "gsr_forward_render_batch", "gsr_forward_batch",
-           "gsr_forward_batch_capacity", "gsr_forward_batch_capacity_raw",
-           "gsr_backward_batch", "gsr_backward_batch_raw", "gsr_backward_depth", "gsr_backward_batch_depth",
-           "gsr_backward_scratch_bytes_depth", "gsr_backward_ext", "gsr_backward_batch_ext", "gsr_alpha_views", "gsr_debug_phase_timing",
+           "gsr_forward_batch_capacity_raw", "gsr_backward_batch", "gsr_backward_batch_ex",
+           "gsr_backward_scratch_bytes_depth", "gsr_alpha_views", "gsr_debug_phase_timing",
            "gsr_image_loss_blocks", "gsr_image_loss_forward", "gsr_image_loss_backward", "gsr_fps", "gsr_fps_scratch_bytes", "gsr_fit_rotations", "gsr_fit_bones", "gsr_fps_thin", "gsr_construct_edges", "gsr_lbs_valid", "gsr_lbs",
            "gsr_rigidity_blocks", "gsr_rigidity_forward", "gsr_rigidity_backward",
            "gsr_views_loss_blocks", "gsr_views_loss_forward", "gsr_views_loss_backward", "gsr_target_moments",
@@ -84,7 +93,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_activate_forward", "gsr_activate_backward", "gsr_adam_step", "gsr_radius_bookkeeping", "gsr_wait_counts",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
-           "gsr_camera_scratch_bytes", "gsr_backward_cam", "gsr_backward_batch_cam")
+           "gsr_camera_scratch_bytes")
 
 
 def load_library():
@@ -112,10 +121,8 @@ def load_library():
     lib.gsr_forward_render.argtypes = [C.POINTER(GsrSettings), i32, u32, vp, vp, vp, vp, vp, vp]
     lib.gsr_backward.restype = C.c_int
     lib.gsr_backward.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 20 + [vp]
-    lib.gsr_backward_depth.restype = C.c_int
-    lib.gsr_backward_depth.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 21 + [vp]
-    lib.gsr_backward_ext.restype = C.c_int
-    lib.gsr_backward_ext.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 22 + [vp]
+    lib.gsr_backward_ex.restype = C.c_int
+    lib.gsr_backward_ex.argtypes = [C.POINTER(GsrSettings), i32, u32] + [vp] * 20 + [C.POINTER(GsrBackwardExtras), vp]
     PS = C.POINTER(GsrSettings)
     PV = C.POINTER(C.c_void_p)
     lib.gsr_batch_state_bytes.restype = sz; lib.gsr_batch_state_bytes.argtypes = [i32, i32, i32, i32]
@@ -129,24 +136,15 @@ def load_library():
     lib.gsr_backward_batch.restype = C.c_int
     lib.gsr_backward_batch.argtypes = ([i32, PS, i32, C.POINTER(u32)] + [vp] * 5 + [PV] * 4 + [vp, C.POINTER(i32), PV, PV]
                                        + [vp, PV, vp, PV, vp, vp, vp, vp, vp])
-    lib.gsr_forward_batch_capacity.restype = C.c_int
-    lib.gsr_forward_batch_capacity.argtypes = ([i32, PS, i32] + [vp] * 5 + [PV, vp, vp] + [PV, PV, PV, C.POINTER(u32), PV, vp,
-                                               C.POINTER(i32), PV, PV, vp, vp])
+    lib.gsr_backward_batch_ex.restype = C.c_int
+    lib.gsr_backward_batch_ex.argtypes = ([i32, PS, i32, C.POINTER(u32)] + [vp] * 5 + [PV] * 4 + [vp, C.POINTER(i32), PV, PV]
+                                          + [vp, PV, vp, PV, vp, vp, vp, vp, C.POINTER(GsrBackwardBatchExtras), vp])
     lib.gsr_forward_batch_capacity_raw.restype = C.c_int
-    lib.gsr_forward_batch_capacity_raw.argtypes = lib.gsr_forward_batch_capacity.argtypes[:-1] + [C.POINTER(GsrRawParams), vp]
-    lib.gsr_backward_batch_raw.restype = C.c_int
-    lib.gsr_backward_batch_raw.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [C.POINTER(GsrRawParams), vp]
-    lib.gsr_backward_batch_depth.restype = C.c_int
-    lib.gsr_backward_batch_depth.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, vp]
-    lib.gsr_backward_batch_ext.restype = C.c_int
-    lib.gsr_backward_batch_ext.argtypes = lib.gsr_backward_batch.argtypes[:-1] + [PV, PV, vp]
+    lib.gsr_forward_batch_capacity_raw.argtypes = ([i32, PS, i32] + [vp] * 5 + [PV, vp, vp] + [PV, PV, PV, C.POINTER(u32), PV, vp,
+                                                   C.POINTER(i32), PV, PV, vp, C.POINTER(GsrRawParams), vp])
     lib.gsr_alpha_views.restype = C.c_int
     lib.gsr_alpha_views.argtypes = [i32, i32, i32, PV, vp, vp]
     lib.gsr_camera_scratch_bytes.restype = sz; lib.gsr_camera_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    lib.gsr_backward_cam.restype = C.c_int
-    lib.gsr_backward_cam.argtypes = lib.gsr_backward_ext.argtypes[:-1] + [C.POINTER(GsrCameraGrads), vp, vp]
-    lib.gsr_backward_batch_cam.restype = C.c_int
-    lib.gsr_backward_batch_cam.argtypes = lib.gsr_backward_batch_ext.argtypes[:-1] + [C.POINTER(GsrCameraGrads), vp, vp]
     lib.gsr_image_loss_blocks.restype = i32
     lib.gsr_image_loss_blocks.argtypes = [i32, i32, i32]
     lib.gsr_image_loss_forward.restype = C.c_int
@@ -415,51 +413,46 @@ def rasterize_backward(state: RasterState, grad_color, means3D, radii, colors_pr
     ``want_color_grad=False`` (precomputed colours that need no gradient): dcolors is None and the blend backward keeps six sums
     per list entry instead of nine.  ``grad_depth`` ([1,H,W] or None): the depth image's gradient (the depth build, its larger
     scratch); ``grad_alpha`` ([1,H,W] or None): the rendered alpha's gradient.  Both None is exactly gsr_backward.
-    ``camera_grads`` (True or four flags for bg, viewmatrix, projmatrix, campos): gsr_backward_cam, and a ninth
+    ``camera_grads`` (True or four flags for bg, viewmatrix, projmatrix, campos): the camera pass, and a ninth
     element (d_bg[3], d_viewmatrix[16], d_projmatrix[16], d_campos[3]) -- flat, in the settings tensors' logical order, None where not
     wanted.  None: eight elements, exactly the call without it."""
     lib = load_library()
     dev = means3D.device
     P, D = state.P, state.num_rendered
-    if camera_grads is not None:
-        want = _camera_want(camera_grads)
-        with _on(dev):
-            rec, cam_out = _camera_outputs(want, dev)
-            cam_scratch = torch.empty((lib.gsr_camera_scratch_bytes(1, P, state.H, state.W),), dtype=torch.uint8, device=dev)
-        if P == 0:     # nothing blended: dL/dbg = the sum of dL/dC, the rest 0
-            with _on(dev):
-                g = grad_color.to(dtype=torch.float32, device=dev).contiguous()
-                _check(lib.gsr_backward_cam(C.byref(state.settings), 0, 0, *([None] * 10), _ptr(g), *([None] * 11), C.byref(rec),
-                                            _ptr(cam_scratch), _stream(dev)), "gsr_backward_cam")
-            return (None,) * 8 + (cam_out,)
+    ex = GsrBackwardExtras()     # bare addresses: rec, cam_scratch, gd and ga stay locals until the call returns
     M = 0 if shs is None else int(shs.shape[1])
     f32 = dict(dtype=torch.float32, device=dev)
     with _on(dev):
-        g = grad_color.to(**f32).contiguous()
-        gd = None if grad_depth is None else grad_depth.to(**f32).contiguous()
-        ga = None if grad_alpha is None else grad_alpha.to(**f32).contiguous()
-        for name, t in (("grad_depth", gd), ("grad_alpha", ga)):
-            if t is not None and t.numel() != state.H * state.W:
-                raise ValueError(f"rasterize_backward: {name} must hold H * W = {state.H * state.W} elements ([1, H, W]), got {t.numel()}")
-        d_means3D = torch.empty((P, 3), **f32)
-        d_means2D = torch.empty((P, 3), **f32)
-        d_colors = torch.empty((P, 3), **f32) if (shs is None and want_color_grad) else None
-        d_opacity = torch.empty((P, 1), **f32)
-        d_scales = torch.empty((P, 3), **f32) if cov3D_precomp is None else None
-        d_rot = torch.empty((P, 4), **f32) if cov3D_precomp is None else None
-        d_cov = torch.empty((P, 6), **f32)
-        d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
-        sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
-        scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
-        args = (C.byref(state.settings), P, D, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(colors_precomp), _ptr(shs),
-                _ptr(cov3D_precomp), _ptr(radii), _ptr(state.geom), _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch),
-                _ptr(d_means3D), _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), _ptr(d_sh),
-                _ptr(gd), _ptr(ga))
         if camera_grads is not None:
-            _check(lib.gsr_backward_cam(*args, C.byref(rec), _ptr(cam_scratch), _stream(dev)), "gsr_backward_cam")
-            return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh, cam_out
-        _check(lib.gsr_backward_ext(*args, _stream(dev)), "gsr_backward_ext")
-    return d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh
+            rec, cam_out = _camera_outputs(_camera_want(camera_grads), dev)
+            cam_scratch = torch.empty((lib.gsr_camera_scratch_bytes(1, P, state.H, state.W),), dtype=torch.uint8, device=dev)
+            ex.cam, ex.cam_scratch = C.addressof(rec), _ptr(cam_scratch)
+        g = grad_color.to(**f32).contiguous()
+        if camera_grads is not None and P == 0:     # nothing blended: dL/dbg = the sum of dL/dC, the rest 0
+            outs = (None,) * 8
+            args = (None,) * 10 + (_ptr(g),) + (None,) * 9
+        else:
+            gd = None if grad_depth is None else grad_depth.to(**f32).contiguous()
+            ga = None if grad_alpha is None else grad_alpha.to(**f32).contiguous()
+            for name, t in (("grad_depth", gd), ("grad_alpha", ga)):
+                if t is not None and t.numel() != state.H * state.W:
+                    raise ValueError(f"rasterize_backward: {name} must hold H * W = {state.H * state.W} elements ([1, H, W]), got {t.numel()}")
+            ex.dL_ddepth, ex.dL_dalpha = _ptr(gd), _ptr(ga)
+            d_means3D = torch.empty((P, 3), **f32)
+            d_means2D = torch.empty((P, 3), **f32)
+            d_colors = torch.empty((P, 3), **f32) if (shs is None and want_color_grad) else None
+            d_opacity = torch.empty((P, 1), **f32)
+            d_scales = torch.empty((P, 3), **f32) if cov3D_precomp is None else None
+            d_rot = torch.empty((P, 4), **f32) if cov3D_precomp is None else None
+            d_cov = torch.empty((P, 6), **f32)
+            d_sh = torch.empty((P, M, 3), **f32) if shs is not None else None
+            sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
+            scratch = torch.empty((sbytes(P, D),), dtype=torch.uint8, device=dev)
+            outs = (d_means3D, d_means2D, d_colors, d_opacity, d_scales, d_rot, d_cov, d_sh)
+            args = (_ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(colors_precomp), _ptr(shs), _ptr(cov3D_precomp), _ptr(radii),
+                    _ptr(state.geom), _ptr(state.binning), _ptr(state.image), _ptr(g), _ptr(scratch)) + tuple(_ptr(o) for o in outs)
+        _check(lib.gsr_backward_ex(C.byref(state.settings), P, D, *args, C.byref(ex), _stream(dev)), "gsr_backward_ex")
+    return outs if camera_grads is None else outs + (cam_out,)
 
 
 MAX_BATCH = 16           # GSR_MAX_BATCH of include/gsr.h: views per library call
@@ -577,7 +570,7 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
         owner = [geometry_of is None or geo[v] == v for v in range(V)]
         cap_e = _entries_capacity.get(key, 0) if (no_host_sync and shs is None and P > 0) else 0
         if cap_e:
-            # Capacity mode (gsr_forward_batch_capacity): no host wait inside the forward.  Buffers are sized for cap_e entries per
+            # Capacity mode (gsr_forward_batch_capacity_raw): no host wait inside the forward.  Buffers are sized for cap_e entries per
             # view; the true counts come back through a pinned copy that `forward_counts_ok` inspects later.  The caller must not
             # let anything of this call escape before that check (gsdyn.step.loss_and_grads_views repeats the call on overflow).
             bbytes = int(lib.gsr_binning_bytes(cap_e, H, W))
@@ -777,7 +770,7 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     into pairs are differentiated unfused; a None entry = no depth gradient for that view).
     ``grad_alpha`` (same forms): the rendered alphas' gradient (fused pairs stay fused; a None entry = no alpha gradient for that view).
     None, or no image at all, for both is exactly gsr_backward_batch.
-    ``camera_grads`` (see rasterize_backward; the same flags for every view): gsr_backward_batch_cam (fused pairs run unfused), and an
+    ``camera_grads`` (see rasterize_backward; the same flags for every view): the camera pass (fused pairs run unfused), and an
     eighth element, a list of V tuples (d_bg, d_viewmatrix, d_projmatrix, d_campos).  SH colours: the single-view path's."""
     lib = load_library()
     dev = means3D.device
@@ -827,24 +820,29 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
                 _ptr_array([stt.image for stt in states]), _ptr(states[0].batch), states[0].geometry_of, per_view(g), _ptr_array(scratch),
                 _ptr(d_means3D), per_view(d_means2D), _ptr(None if (per_view_col or not want_color_grad) else d_colors),
                 per_view(d_colors) if (per_view_col and want_color_grad) else None)
+        ex = GsrBackwardBatchExtras()     # bare addresses: rawp, recs, gd_arr, ga_arr and cam_scratch stay locals until the call returns
+        if gd is not None:
+            gd_arr = _ptr_array(gd)
+            ex.dL_ddepth_views = C.addressof(gd_arr)
+        if ga is not None:
+            ga_arr = _ptr_array(ga)
+            ex.dL_dalpha_views = C.addressof(ga_arr)
+        plain = (_ptr(d_opacity), _ptr(d_scales), _ptr(d_rot))
         if fused is not None:    # the chain through the activations runs inside the per-Gaussian kernel: d_rot / d_opacity / d_scales
-            #                      come back as the gradients of the UNACTIVATED parameters (same shapes)
+            #                      come back as the gradients of the UNACTIVATED parameters (same shapes), through the record
             rawp = GsrRawParams(_ptr(fused[0]), None, None, _ptr(rotations), _ptr(states[0].act[1]), _ptr(scales),
                                 _ptr(d_rot), _ptr(d_opacity), _ptr(d_scales))
-            rc = lib.gsr_backward_batch_raw(*args, None, None, None, _ptr(d_cov), C.byref(rawp), _stream(dev))
-        elif want is not None:     # camera gradients: one record per view, the camera pass behind the per-Gaussian backward
+            ex.raw = C.addressof(rawp)
+            plain = (None, None, None)
+        if want is not None:     # camera gradients: one record per view, the camera pass behind the per-Gaussian backward
             recs = (GsrCameraGrads * V)()
             cam_out = []
             for v in range(V):
                 recs[v], o = _camera_outputs(want, dev)
                 cam_out.append(o)
             cam_scratch = torch.empty((lib.gsr_camera_scratch_bytes(V, P, states[0].H, states[0].W),), dtype=torch.uint8, device=dev)
-            rc = lib.gsr_backward_batch_cam(*args, _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
-                                            None if gd is None else _ptr_array(gd), None if ga is None else _ptr_array(ga), recs,
-                                            _ptr(cam_scratch), _stream(dev))
-        else:
-            rc = lib.gsr_backward_batch_ext(*args, _ptr(d_opacity), _ptr(d_scales), _ptr(d_rot), _ptr(d_cov),
-                                            None if gd is None else _ptr_array(gd), None if ga is None else _ptr_array(ga), _stream(dev))
+            ex.cams, ex.cam_scratch = C.addressof(recs), _ptr(cam_scratch)
+        rc = lib.gsr_backward_batch_ex(*args, *plain, _ptr(d_cov), C.byref(ex), _stream(dev))
         _check(rc, "gsr_backward_batch")
     # without a colour gradient, views that share a camera stay fused in the backward (one replay of the tile lists for both)
     res = (d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None)

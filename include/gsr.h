@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GSR_VERSION 124 /* 0.1.24 -- the history of the ABI is in CHANGELOG.md ("ABI history") */
+#define GSR_VERSION 125 /* 0.1.25 -- the history of the ABI is in CHANGELOG.md ("ABI history") */
 #define GSR_TILE 16     /* tiles are 16x16 pixels, as in the reference extension */
 
 /* Mirror of GaussianRasterizationSettings (/root/reference/src/tracking/helpers.py:20-32).
@@ -72,8 +72,8 @@ size_t gsr_geom_bytes(int32_t P);
 size_t gsr_image_bytes(int32_t image_height, int32_t image_width);
 size_t gsr_binning_bytes(uint32_t num_rendered, int32_t image_height, int32_t image_width);
 size_t gsr_backward_scratch_bytes(int32_t P, uint32_t num_rendered);
-/* scratch of gsr_backward_depth / gsr_backward_batch_depth: gsr_backward_scratch_bytes(P, num_rendered) for the records, then one
- * float of dL/dz per list entry */
+/* scratch of a backward with a depth gradient (gsr_backward_extras.dL_ddepth, gsr_backward_batch_extras.dL_ddepth_views):
+ * gsr_backward_scratch_bytes(P, num_rendered) for the records, then one float of dL/dz per list entry */
 size_t gsr_backward_scratch_bytes_depth(int32_t P, uint32_t num_rendered);
 
 /* ---- forward, stage 1  (replaces the first half of `rasterize_gaussians`: preprocess + offsets scan)
@@ -100,14 +100,14 @@ int gsr_forward_render(const gsr_settings* s, int32_t P, uint32_t num_rendered, 
  * the geometry state of an earlier forward of the same P and image size (prev_geom_state; it must outlive the call): per Gaussian the entry
  * count, tile rect, tile mask, depth bits and -- because the forward leaves the backward's per-quad contribution bytes in the binning
  * state, next to the lists, so a sharer rewrites the owner's bytes and they must be the same bytes -- 2D mean, conic and opacity; colours
- * may differ.  *same_host = 1: everything equal (then num_rendered is equal too) -- the second forward may call gsr_forward_render_shared
- * with the first call's binning and image states instead of gsr_forward_render: no duplicates are emitted or sorted, its own image state
+ * may differ.  *same_host = 1: everything equal (then num_rendered is equal too) -- the second forward may call gsr_forward_render_shared_ex
+ * with the first call's binning and image states instead of gsr_forward_render_ex: no duplicates are emitted or sorted, its own image state
  * receives a copy of the owner's ranges and tile order, and gsr_backward takes (own geom, OWNER's binning, own image) as usual.
  * 0: something differs, or no comparison was made (prev_geom_state NULL, P > 512 Ki).  The verdict rides in the copy that brings the entry
  * count back: no extra synchronisation; the comparison reads 84 bytes per Gaussian (~3 us at 100 k).  (ABI <= 119 compared a 64-bit
  * fingerprint: equal "up to a 2^-64 coincidence"; the bar for integer work is bit-exact.)
  * Results are bit-identical to gsr_forward_render. */
-/* gsr_forward_render_ex / gsr_forward_render_shared_ex (ABI 119): the same with `flags` -- GSR_FORWARD_ONLY (defined below): the caller
+/* `flags` of gsr_forward_render_ex / gsr_forward_render_shared_ex (ABI 119; 0 = gsr_forward_render) -- GSR_FORWARD_ONLY (defined below): the caller
  * will not run gsr_backward on these states, so the blend skips recording what only a backward reads (the per-entry contribution bytes
  * and the per-Gaussian used flags: 7 % of a forward).  The torch layer passes it when no input of the call requires a gradient. */
 int gsr_forward_render_ex(const gsr_settings* s, int32_t P, uint32_t num_rendered, const void* geom_state, void* binning_state,
@@ -119,9 +119,6 @@ int gsr_forward_preprocess_same(const gsr_settings* s, int32_t P, const float* m
                                 const float* rotations, const float* opacities, const float* colors_precomp,
                                 const float* shs, const float* cov3D_precomp, void* geom_state, int32_t* radii,
                                 uint32_t* num_rendered_host, const void* prev_geom_state, int32_t* same_host, void* stream);
-int gsr_forward_render_shared(const gsr_settings* s, int32_t P, uint32_t num_rendered, void* geom_state,
-                              void* owner_binning_state, const void* owner_image_state, void* image_state, float* out_color,
-                              float* out_depth, void* stream);
 
 /* ---- the single-view forward WITHOUT a host wait inside (ABI 121; upstream reads num_rendered back in the middle of its forward,
  * rasterizer_impl.cu -- reached from /root/reference/src/tracking/train_utils.py:178 and src/render/renderer.py:22 -- and the GPU idles
@@ -130,7 +127,7 @@ int gsr_forward_render_shared(const gsr_settings* s, int32_t P, uint32_t num_ren
  * count with some slack), every kernel clamps to it, and the true count arrives in *count_pinned -- PINNED host memory that the caller
  * pre-set to -1 -- by a system-scope store of the tile-order kernel: wait with gsr_wait_counts (no stream synchronisation) once all the
  * call's launches are queued.  count <= capacity_entries: the outputs and states are valid, and `capacity_entries` is the num_rendered
- * that gsr_backward, gsr_forward_render_shared and gsr_backward_scratch_bytes must be given for these states (it fixed their layout).
+ * that gsr_backward, gsr_forward_render_shared_ex and gsr_backward_scratch_bytes must be given for these states (it fixed their layout).
  * count > capacity_entries: nothing of the call may be used -- repeat with gsr_forward_preprocess + gsr_forward_render.
  * Earlier still (P <= 512 Ki): block_words_pinned -- pinned host memory, 8-BYTE ALIGNED, 2 * ceil(P / 256) words, the ODD words pre-set to 0xffffffff by the
  * caller.  Every preprocess block stores {differs, its entry count} there with one 8-byte store; gsr_wait_block_counts polls the words and
@@ -155,37 +152,13 @@ int64_t gsr_wait_block_counts(const volatile uint32_t* words, int32_t nblk, int6
  * training, /root/reference/src/tracking/train_utils.py:133,155): the blend backward then keeps six sums per list entry instead
  * of nine.  Every other gradient is the same up to the rounding of a different reduction tree.
  * gsr_backward takes no incoming gradient for radii or depth: they are ignored by contract (no reference call site differentiates
- * them, /root/reference/src/tracking/train_utils.py:178,192).  The depth gradient is gsr_backward_depth's (below). */
+ * them, /root/reference/src/tracking/train_utils.py:178,192).  It is gsr_backward_ex (below) with ex == NULL. */
 int gsr_backward(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
                  const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
                  const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
                  const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
                  float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, void* stream);
-/* gsr_backward with an incoming gradient for the depth image: dL_ddepth [1,H,W] (device).  The depth D = sum_i alpha_i T_i z_i (z_i:
- * Gaussian i's view-space depth, no background term) is differentiated as a fourth colour channel whose colour is z_i and whose
- * background is 0, plus the chain z_i -> means3D, dz/dmeans3D = (view[2], view[6], view[10]) of the column-major viewmatrix.  The
- * depth term changes dL/dalpha, so it reaches every gradient, not only dL_dmeans3D.  `scratch` must hold
- * gsr_backward_scratch_bytes_depth(P, num_rendered) bytes.  dL_ddepth == NULL: exactly gsr_backward (same kernels, same result). */
-int gsr_backward_depth(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                       const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                       const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                       const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                       float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth, void* stream);
-/* gsr_backward with incoming gradients for the depth image AND the rendered alpha: dL_dalpha [1,H,W] (device) differentiates
- * A = 1 - final_T (gsr_alpha_views).  dA/dalpha_i = final_T / (1 - alpha_i) has the background term's form, so the alpha gradient only
- * adds final_T * dL_dalpha to that per-pixel term of the blend backward: it reaches dL_dmeans2D, the conic (dL_dscales, dL_drotations,
- * dL_dcov3D), dL_dopacity and dL_dmeans3D, never dL_dcolors / dL_dsh.  The 0.99 clamp, the 1/255 cut and the T < 1e-4 stop are the
- * forward's.  `scratch`: gsr_backward_scratch_bytes(P, num_rendered) when dL_ddepth is NULL, gsr_backward_scratch_bytes_depth otherwise
- * (then gsr_backward_depth's rules hold).  dL_dalpha == NULL: exactly gsr_backward_depth (and with dL_ddepth NULL too, gsr_backward). */
-int gsr_backward_ext(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                     const float* dL_dalpha, void* stream);
 /* Camera gradients (opt-in): dL/d(viewmatrix, projmatrix, campos, bg) of one view, fp32 device arrays of 16, 16, 3
  * and 3 floats laid out like the gsr_settings members (the matrices column-major as stored).  A NULL member: that gradient is not wanted.
  * viewmatrix[3, 7, 11, 15] and projmatrix[2, 6, 10, 14] are never read by the forward: their gradient is 0.  campos reaches the render
@@ -199,19 +172,35 @@ typedef struct gsr_camera_grads {
 } gsr_camera_grads;
 /* device scratch of the camera pass (one fp64 row per workgroup and view), for V views of P Gaussians and H x W pixels */
 size_t gsr_camera_scratch_bytes(int32_t V, int32_t P, int32_t H, int32_t W);
-/* gsr_backward_ext plus the camera gradients `cam` (host record of device pointers).  The camera pass runs behind the per-Gaussian
- * backward on `stream`, over the same records: a second walk of each Gaussian's records with the fp64 chain, a reduction without atomics
- * (bit-identical from run to run), and sum_pixels final_T dL/dC for bg.  `cam_scratch`: gsr_camera_scratch_bytes(1, P, H, W) bytes.
- * Every other output is gsr_backward_ext's, bit for bit.  When the blend backward aborted (GSR_QUEUE_BWD_ERROR) the camera outputs are
- * NaN, as dL_dmeans3D is.  P = 0: dL_dbg = sum of dL_dcolor, the rest 0 (geom / image state may then be NULL).
- * cam == NULL: exactly gsr_backward_ext. */
-int gsr_backward_cam(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
-                     const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
-                     const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
-                     const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
-                     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const float* dL_ddepth,
-                     const float* dL_dalpha, const gsr_camera_grads* cam, void* cam_scratch, void* stream);
+/* The opt-in parts of the single-view backward (host record).  Every member is independent of the others; a NULL member switches its part
+ * off, and the all-NULL record (or ex == NULL) is exactly gsr_backward: same kernels, same result, bit for bit. */
+typedef struct gsr_backward_extras {
+  /* Incoming gradient of the depth image, [1,H,W] device.  The depth D = sum_i alpha_i T_i z_i (z_i: Gaussian i's view-space depth, no
+   * background term) is differentiated as a fourth colour channel whose colour is z_i and whose background is 0, plus the chain
+   * z_i -> means3D, dz/dmeans3D = (view[2], view[6], view[10]) of the column-major viewmatrix.  The depth term changes dL/dalpha, so it
+   * reaches every gradient, not only dL_dmeans3D.  `scratch` must then hold gsr_backward_scratch_bytes_depth(P, num_rendered) bytes
+   * (gsr_backward_scratch_bytes otherwise). */
+  const float* dL_ddepth;
+  /* Incoming gradient of the rendered alpha A = 1 - final_T (gsr_alpha_views), [1,H,W] device.  dA/dalpha_i = final_T / (1 - alpha_i) has
+   * the background term's form, so it only adds final_T * dL_dalpha to that per-pixel term of the blend backward: it reaches dL_dmeans2D,
+   * the conic (dL_dscales, dL_drotations, dL_dcov3D), dL_dopacity and dL_dmeans3D, never dL_dcolors / dL_dsh.  The 0.99 clamp, the 1/255
+   * cut and the T < 1e-4 stop are the forward's.  Needs no scratch of its own. */
+  const float* dL_dalpha;
+  /* Camera gradients wanted (host record of device pointers), with cam_scratch: gsr_camera_scratch_bytes(1, P, H, W) bytes (device).  The
+   * camera pass runs behind the per-Gaussian backward on `stream`, over the same records: a second walk of each Gaussian's records with
+   * the fp64 chain, a reduction without atomics (bit-identical from run to run), and sum_pixels final_T dL/dC for bg.  Every other output
+   * is what the call writes without `cam`, bit for bit.  When the blend backward aborted (GSR_QUEUE_BWD_ERROR) the camera outputs are NaN,
+   * as dL_dmeans3D is.  P = 0: dL_dbg = sum of dL_dcolor, the rest 0 (geom / image state may then be NULL). */
+  const gsr_camera_grads* cam;
+  void* cam_scratch;
+} gsr_backward_extras;
+int gsr_backward_ex(const gsr_settings* s, int32_t P, uint32_t num_rendered, const float* means3D,
+                    const float* scales, const float* rotations, const float* colors_precomp, const float* shs,
+                    const float* cov3D_precomp, const int32_t* radii, const void* geom_state,
+                    const void* binning_state, const void* image_state, const float* dL_dcolor, void* scratch,
+                    float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity,
+                    float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dsh, const gsr_backward_extras* ex,
+                    void* stream);
 /* The rendered alpha of V forwards of one image size, one launch: out_alpha[v * H * W + pix] = 1 - final_T of image_states[v] (device,
  * [V,H,W] contiguous), bit for bit the forward's own transmittance; 0 where nothing was blended.  Valid after any forward of those states
  * (single view, shared lists, batch, capacity mode, fused pairs, forward-only, depth cuts).  V in 1..GSR_MAX_BATCH. */
@@ -278,9 +267,6 @@ int gsr_forward_batch(int32_t V, const gsr_settings* s, int32_t P, const float* 
                       void* const* binning_states, const size_t* binning_bytes, void* const* image_states,
                       void* batch_state, const int32_t* geometry_of, float* const* out_color, float* const* out_depth,
                       uint32_t* num_rendered_host, int32_t flags, void* stream);
-/* Backward of all V views (precomputed colours only; with SH use gsr_backward per view): ONE blend-backward launch
- * over the combined tile queue, then ONE per-Gaussian kernel that loops over the views and writes the
- * gradients SUMMED over views.  Only dL_dmeans2D stays per view ([V] pointers to [P,3]). */
 /* Capacity mode of gsr_forward_batch: NO host synchronisation.  The caller sizes every binning buffer for `capacity_entries[v]`
  * list entries (gsr_binning_bytes(capacity_entries[v], H, W); a view with geometry_of[v] != v repeats its owner's capacity) and
  * keeps passing those capacities as `num_rendered` to gsr_backward_batch (they fix the buffer layouts; scratch:
@@ -289,21 +275,14 @@ int gsr_forward_batch(int32_t V, const gsr_settings* s, int32_t P, const float* 
  * anything of that call and repeat it with enough room (gsdyn/step.py: loss_and_grads_views does, its images never leave
  * the library).  The kernels read the counts on the device (the word emit_entries leaves behind the offsets).
  * counts_dev may be device memory or device-mapped PINNED HOST memory (hipHostMalloc): the counts are written with system-scope
- * stores by the tile-order kernel, so a host that waits for any later event of the stream reads them without a copy. */
-int gsr_forward_batch_capacity(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* scales,
-                               const float* rotations, const float* opacities, const float* colors_precomp,
-                               const float* const* colors_views, const float* shs, const float* cov3D_precomp,
-                               void* const* geom_states, int32_t* const* radii, void* const* binning_states,
-                               const uint32_t* capacity_entries, void* const* image_states, void* batch_state,
-                               const int32_t* geometry_of, float* const* out_color, float* const* out_depth,
-                               uint32_t* counts_dev, void* stream);
-/* ---- raw-parameter mode (the tracking step, /root/reference/src/tracking/helpers.py:36-45): the caller holds unnormalised
+ * stores by the tile-order kernel, so a host that waits for any later event of the stream reads them without a copy.
+ * ---- raw-parameter mode (the tracking step, /root/reference/src/tracking/helpers.py:36-45): the caller holds unnormalised
  * rotations, logit opacities and log scales; their activations (normalize / sigmoid / exp) and the chain back through them are
  * applied INSIDE the per-Gaussian kernels of the forward and the backward instead of in two launches of their own.
  * Forward: the activated values are also written to rotations_out / opacities_out / scales_out -- the SAME buffers must be passed
  * as the call's `rotations` / `opacities` / `scales` arguments (and again to the backward).  Backward: the parameter gradients go
  * to d_unnorm_rotations / d_logit_opacities / d_log_scales; dL_drotations / dL_dopacity / dL_dscales may then be NULL.
- * Values are bit-identical to gsr_activate_forward / gsr_activate_backward. */
+ * Values are bit-identical to gsr_activate_forward / gsr_activate_backward.  cov3D_precomp excludes raw parameters (-2). */
 typedef struct gsr_raw_params {
   const float* unnorm_rotations;   /* [P,4] */
   const float* logit_opacities;    /* [P]   */
@@ -315,7 +294,7 @@ typedef struct gsr_raw_params {
   float* d_logit_opacities;        /* backward: [P]   */
   float* d_log_scales;             /* backward: [P,3] */
 } gsr_raw_params;
-/* gsr_forward_batch_capacity / gsr_backward_batch with the activations fused (raw == NULL: exactly those functions). */
+/* The capacity-mode forward; raw == NULL: the activated values are the caller's. */
 int gsr_forward_batch_capacity_raw(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* scales,
                                    const float* rotations, const float* opacities, const float* colors_precomp,
                                    const float* const* colors_views, const float* shs, const float* cov3D_precomp,
@@ -323,13 +302,10 @@ int gsr_forward_batch_capacity_raw(int32_t V, const gsr_settings* s, int32_t P, 
                                    const uint32_t* capacity_entries, void* const* image_states, void* batch_state,
                                    const int32_t* geometry_of, float* const* out_color, float* const* out_depth,
                                    uint32_t* counts_dev, const gsr_raw_params* raw, void* stream);
-int gsr_backward_batch_raw(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                           const float* scales, const float* rotations, const float* colors_precomp,
-                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                           void* const* binning_states, void* const* image_states, void* batch_state,
-                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_raw_params* raw, void* stream);
+/* Backward of all V views (precomputed colours only; with SH use gsr_backward per view): ONE blend-backward launch
+ * over the combined tile queue, then ONE per-Gaussian kernel that loops over the views and writes the
+ * gradients SUMMED over views.  Only dL_dmeans2D stays per view ([V] pointers to [P,3]).  It is gsr_backward_batch_ex (below) with
+ * ex == NULL. */
 int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
                        const float* scales, const float* rotations, const float* colors_precomp,
                        const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
@@ -337,42 +313,34 @@ int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32
                        const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
                        float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                        float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* stream);
-/* gsr_backward_batch with depth gradients (see gsr_backward_depth): dL_ddepth_views[V] device pointers to [1,H,W], a NULL entry = no
- * depth gradient for that view.  With any entry set, every view's scratch must hold gsr_backward_scratch_bytes_depth(P, num_rendered[v])
- * bytes, and views the forward fused into pairs are differentiated unfused (the depth build has no pair pass).  dL_ddepth_views == NULL
- * or all entries NULL: exactly gsr_backward_batch. */
-int gsr_backward_batch_depth(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                             const float* scales, const float* rotations, const float* colors_precomp,
-                             const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                             void* const* binning_states, void* const* image_states, void* batch_state,
-                             const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                             float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                             float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                             void* stream);
-/* gsr_backward_batch with depth and alpha gradients (see gsr_backward_ext): dL_dalpha_views[V] device pointers to [1,H,W], a NULL entry
- * = no alpha gradient for that view.  The depth rules are gsr_backward_batch_depth's; alpha alone keeps fused pairs fused (each view of a
- * pair adds its own alpha term).  dL_dalpha_views == NULL: exactly gsr_backward_batch_depth. */
-int gsr_backward_batch_ext(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                           const float* scales, const float* rotations, const float* colors_precomp,
-                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                           void* const* binning_states, void* const* image_states, void* batch_state,
-                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                           const float* const* dL_dalpha_views, void* stream);
-
-/* gsr_backward_batch_ext plus the camera gradients of every view: cams[V] (host array of records, see gsr_camera_grads).  Views the forward
- * fused into pairs are differentiated unfused (the camera pass needs each view's own records).  `cam_scratch`:
- * gsr_camera_scratch_bytes(V, P, H, W) bytes.  Every other output is gsr_backward_batch_ext's for an unfused call.  cams == NULL: exactly
- * gsr_backward_batch_ext. */
-int gsr_backward_batch_cam(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
-                           const float* scales, const float* rotations, const float* colors_precomp,
-                           const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
-                           void* const* binning_states, void* const* image_states, void* batch_state,
-                           const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
-                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
-                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const float* const* dL_ddepth_views,
-                           const float* const* dL_dalpha_views, const gsr_camera_grads* cams, void* cam_scratch, void* stream);
+/* The opt-in parts of the batch backward (host record; the tables are host arrays of V entries).  A NULL member switches its part off,
+ * and the all-NULL record (or ex == NULL) is exactly gsr_backward_batch, bit for bit.  What each part differentiates is described at
+ * gsr_backward_extras; below, what the batch adds.  `raw` excludes every other member (-2). */
+typedef struct gsr_backward_batch_extras {
+  /* Raw-parameter mode (gsr_raw_params above): the chain through the activations runs inside the per-Gaussian kernel.  Rejected (-2)
+   * together with cov3D_precomp, with `cams`, and with a depth or alpha table. */
+  const gsr_raw_params* raw;
+  /* [V] device pointers to [1,H,W]; a NULL entry = no depth gradient for that view (the table with every entry NULL is the NULL table).
+   * With any entry set, every view's scratch must hold gsr_backward_scratch_bytes_depth(P, num_rendered[v]) bytes, and views the
+   * forward fused into pairs are differentiated unfused (the depth build has no pair pass). */
+  const float* const* dL_ddepth_views;
+  /* [V] device pointers to [1,H,W]; a NULL entry = no alpha gradient for that view.  Alpha alone keeps fused pairs fused (each view of
+   * a pair adds its own alpha term). */
+  const float* const* dL_dalpha_views;
+  /* [V] records, one per view, with cam_scratch: gsr_camera_scratch_bytes(V, P, H, W) bytes (device).  Views the forward fused into
+   * pairs are differentiated unfused (the camera pass needs each view's own records); every other output is the unfused call's.  The
+   * NaN poisoning on GSR_QUEUE_BWD_ERROR and the P = 0 result are the single-view rules, per view. */
+  const gsr_camera_grads* cams;
+  void* cam_scratch;
+} gsr_backward_batch_extras;
+int gsr_backward_batch_ex(int32_t V, const gsr_settings* s, int32_t P, const uint32_t* num_rendered, const float* means3D,
+                          const float* scales, const float* rotations, const float* colors_precomp,
+                          const float* cov3D_precomp, const int32_t* const* radii, void* const* geom_states,
+                          void* const* binning_states, void* const* image_states, void* batch_state,
+                          const int32_t* geometry_of, const float* const* dL_dcolor, void* const* scratch, float* dL_dmeans3D,
+                          float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
+                          float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_backward_batch_extras* ex,
+                          void* stream);
 /* ---- neighbour terms of the t > 0 tracking loss, fused (caller side of the path):
  *   rigid, rot, iso of /root/reference/src/tracking/train_utils.py:198-222 as three means over (foreground point, neighbour).
  * All per-point arrays are indexed by foreground rank; fg_idx[n_fg] (int64) maps rank -> Gaussian; neighbor_* are [n_fg,K];
@@ -632,7 +600,7 @@ typedef struct gsr_kernel_time {
 int gsr_profile_begin(void);
 int gsr_profile_end(gsr_kernel_time* out, int32_t max_entries, int32_t* n_out);
 
-/* Host side of the capacity-mode forward (gsr_forward_batch_capacity*): the tile-order kernel stores every view's entry count with
+/* Host side of the capacity-mode forward (gsr_forward_batch_capacity_raw): the tile-order kernel stores every view's entry count with
  * system-scope stores into the caller's PINNED host array `counts` (pre-set to -1 by the caller).  gsr_wait_counts spins on that
  * array from C -- no device call, no stream synchronisation, nothing of the caller's runtime (a Python caller's interpreter lock is
  * released for the duration by ctypes) -- until all `n` values are >= 0 and returns their maximum; -1 after `timeout_us`

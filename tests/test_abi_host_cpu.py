@@ -26,13 +26,66 @@ def test_library_exports_every_declared_symbol():
 def test_host_only_entry_points_work_without_a_gpu():
     from diff_gaussian_rasterization import _hip
     lib = _hip.load_library()
-    assert lib.gsr_version() == 124
+    assert lib.gsr_version() == 125
     g1, g2 = lib.gsr_geom_bytes(1000), lib.gsr_geom_bytes(100000)
     assert 0 < g1 < g2 and g2 % 256 == 0
     assert lib.gsr_image_bytes(800, 800) >= 800 * 800 * 8 + 2500 * 8
     assert lib.gsr_binning_bytes(0, 800, 800) > 0
     assert lib.gsr_binning_bytes(460000, 800, 800) >= 460000 * (4 + 4 + 8 + 8 + 4)
     assert lib.gsr_backward_scratch_bytes(100000, 460000) >= 460000 * 36
+
+
+REMOVED_IN_ABI_125 = ("gsr_backward_depth", "gsr_backward_ext", "gsr_backward_cam", "gsr_backward_batch_raw", "gsr_backward_batch_depth",
+                      "gsr_backward_batch_ext", "gsr_backward_batch_cam", "gsr_forward_render_shared", "gsr_forward_batch_capacity")
+
+
+def test_backward_entry_points_are_one_per_shape():
+    """ABI 125: the backward is gsr_backward / gsr_backward_batch plus their _ex forms that take the opt-in parts in a record; the
+    per-feature entry points (and the two forward twins nobody called) are gone from the header and from the library."""
+    from diff_gaussian_rasterization import _hip
+    hdr = open(os.path.join(ROOT, "include", "gsr.h")).read()
+    assert set(re.findall(r"\b(gsr_backward\w*)\(", hdr)) == {
+        "gsr_backward", "gsr_backward_ex", "gsr_backward_batch", "gsr_backward_batch_ex", "gsr_backward_scratch_bytes",
+        "gsr_backward_scratch_bytes_depth"}
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    for name in REMOVED_IN_ABI_125:
+        assert not hasattr(lib, name), f"{name} was removed in ABI 125 but is still exported"
+        assert name not in _hip.EXPORTS
+
+
+def _header_members(hdr, name):
+    """Member names of ``typedef struct <name> { ... } <name>;`` in declaration order (comments stripped)."""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [re.search(r"(\w+)\s*$", decl).group(1) for decl in body.split(";") if decl.strip()]
+
+
+def test_extras_records_mirror_the_header():
+    """The ctypes mirrors of gsr_backward_extras / gsr_backward_batch_extras cannot drift from include/gsr.h: pointer-only records of
+    4 and 5 members, the same names in the same order."""
+    from diff_gaussian_rasterization import _hip
+    hdr = open(os.path.join(ROOT, "include", "gsr.h")).read()
+    ptr = ctypes.sizeof(ctypes.c_void_p)
+    for cls, name, n in ((_hip.GsrBackwardExtras, "gsr_backward_extras", 4), (_hip.GsrBackwardBatchExtras, "gsr_backward_batch_extras", 5)):
+        assert ctypes.sizeof(cls) == n * ptr
+        assert all(ctypes.sizeof(f[1]) == ptr for f in cls._fields_)
+        assert [f[0] for f in cls._fields_] == _header_members(hdr, name)
+    assert _header_members(hdr, "gsr_backward_extras") == ["dL_ddepth", "dL_dalpha", "cam", "cam_scratch"]
+    assert _header_members(hdr, "gsr_backward_batch_extras") == ["raw", "dL_ddepth_views", "dL_dalpha_views", "cams", "cam_scratch"]
+
+
+def test_backward_ex_rejects_null_settings_on_the_host():
+    """Both backward bodies check the settings before they touch the device: NULL settings is -2 with a message, with or without a record."""
+    from diff_gaussian_rasterization import _hip
+    lib = _hip.load_library()
+    for ex in (None, ctypes.byref(_hip.GsrBackwardExtras())):
+        assert lib.gsr_backward_ex(None, 10, 0, *([None] * 20), ex, None) == -2
+        assert b"settings" in lib.gsr_last_error()
+    for ex in (None, ctypes.byref(_hip.GsrBackwardBatchExtras())):
+        assert lib.gsr_backward_batch_ex(2, None, 10, *([None] * 22), ex, None) == -2
+        assert b"settings" in lib.gsr_last_error()
+    assert lib.gsr_backward(None, 10, 0, *([None] * 21)) == -2
+    assert lib.gsr_backward_batch(2, None, 10, *([None] * 23)) == -2
 
 
 def test_host_only_size_functions_of_the_step_kernels():

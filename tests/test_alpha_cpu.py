@@ -14,7 +14,7 @@ from oracle.dense_oracle import dense_rasterize, finite_difference
 from util import random_gaussians, ring_camera
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("gsr_alpha_views", "gsr_backward_ext", "gsr_backward_batch_ext")
+SYMBOLS = ("gsr_alpha_views", "gsr_backward_ex", "gsr_backward_batch_ex")
 
 
 def test_abi_exports():

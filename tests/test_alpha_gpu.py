@@ -461,7 +461,7 @@ def test_multiview_equals_sum_of_single_views(dev):
 @pytest.mark.parametrize("depth", [False, True])
 def test_multiview_fused_pair(dev, monkeypatch, depth):
     """Views 0 and 1 share one camera (ONE settings object) and have different frozen colours: the forward fuses them (geometry_of =
-    [0, 0, 2]).  With alpha alone the backward keeps the pair fused (gsr_backward_batch_ext, no depth entries: the pair pass adds each
+    [0, 0, 2]).  With alpha alone the backward keeps the pair fused (gsr_backward_batch_ex, no depth entries: the pair pass adds each
     view's own alpha term); with depth as well it runs unfused.  Either way: the sum of one single-view call per view, and a second
     retain_graph backward repeats the first."""
     P, W, H = 2000, 128, 96

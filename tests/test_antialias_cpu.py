@@ -23,7 +23,7 @@ def test_header_bit_and_exports():
     with open(os.path.join(ROOT, "include", "gsr.h")) as f:
         h = f.read()
     assert re.search(r"^#define GSR_SETTINGS_ANTIALIASING 2\b", h, re.M)
-    assert re.search(r"^#define GSR_VERSION 124\b", h, re.M)
+    assert re.search(r"^#define GSR_VERSION 125\b", h, re.M)
     assert _hip.ANTIALIASING == 2
     lib = ctypes.CDLL(_hip.LIB_PATH)          # dlopen works without a GPU
     for sym in _hip.EXPORTS:

@@ -397,7 +397,7 @@ def test_mixed_flags_and_unknown_bits_are_rejected(dev):
     batch = torch.empty((4096,), dtype=torch.uint8, device=dev)
     rc = lib.gsr_forward_batch(2, sarr, 10, *([None] * 13), C.c_void_p(batch.data_ptr()), None, None, None, None, 0, None)
     assert rc == -2 and b"GSR_SETTINGS_ANTIALIASING" in lib.gsr_last_error()
-    rc = lib.gsr_backward_batch_ext(2, sarr, 10, *([None] * 10), C.c_void_p(batch.data_ptr()), *([None] * 14))
+    rc = lib.gsr_backward_batch_ex(2, sarr, 10, *([None] * 10), C.c_void_p(batch.data_ptr()), *([None] * 13))
     assert rc == -2 and b"GSR_SETTINGS_ANTIALIASING" in lib.gsr_last_error()
     s0.prefiltered = 4
     rc = lib.gsr_forward_preprocess(C.byref(s0), 10, *([None] * 11))

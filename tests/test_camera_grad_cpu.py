@@ -19,13 +19,13 @@ def test_exports_version_and_scratch():
     from diff_gaussian_rasterization import _hip
     with open(os.path.join(ROOT, "include", "gsr.h")) as f:
         h = f.read()
-    assert re.search(r"^#define GSR_VERSION 124\b", h, re.M)
+    assert re.search(r"^#define GSR_VERSION 125\b", h, re.M)
     assert "typedef struct gsr_camera_grads" in h
     lib = ctypes.CDLL(_hip.LIB_PATH)          # dlopen works without a GPU
-    for sym in ("gsr_backward_cam", "gsr_backward_batch_cam", "gsr_camera_scratch_bytes"):
+    for sym in ("gsr_backward_ex", "gsr_backward_batch_ex", "gsr_camera_scratch_bytes"):
         assert sym in _hip.EXPORTS
         getattr(lib, sym)
-    assert lib.gsr_version() == 124
+    assert lib.gsr_version() == 125
     lib = _hip.load_library()
     b = lib.gsr_camera_scratch_bytes
     assert b(1, 100, 96, 80) > 0 and b(1, 0, 96, 80) > 0

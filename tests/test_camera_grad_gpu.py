@@ -292,7 +292,7 @@ def test_views_equal_single_views(dev, V):
 
 def test_fused_pairs_run_unfused(dev, monkeypatch):
     """Two views with the same camera tensors and their own frozen colours: the forward fuses them, the camera-gradient backward goes
-    through gsr_backward_batch_cam (unfused), and the shared camera tensors get the sum of two separately rendered views' gradients."""
+    through gsr_backward_batch_ex's camera records (unfused), and the shared camera tensors get the sum of two separately rendered views' gradients."""
     from diff_gaussian_rasterization import _hip
     W, H = 64, 48
     g, _ = _scene("precomp", 300, seed=6)

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_abi_exports():
     from diff_gaussian_rasterization import _hip
     lib = ctypes.CDLL(_hip.LIB_PATH)          # dlopen works without a GPU
-    for sym in ("gsr_backward_depth", "gsr_backward_batch_depth", "gsr_backward_scratch_bytes_depth"):
+    for sym in ("gsr_backward_ex", "gsr_backward_batch_ex", "gsr_backward_scratch_bytes_depth"):
         getattr(lib, sym)
         assert sym in _hip.EXPORTS
     sz, i32, u32 = ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32

@@ -312,7 +312,7 @@ def _spy(monkeypatch, name, rewrite=None):
 
 
 def _depth_only_for(views):
-    """A rasterize_backward_batch rewrite: NULL depth gradient (None) for every view not in ``views`` (gsr_backward_batch_ext's NULL
+    """A rasterize_backward_batch rewrite: NULL depth gradient (None) for every view not in ``views`` (gsr_backward_batch_ex's NULL
     entries; autograd itself always hands the whole [V,1,H,W] image)."""
     def rw(k):
         gd = k.get("grad_depth")
@@ -345,7 +345,7 @@ def test_multiview_equals_sum_of_single_views(dev):
 
 
 def test_multiview_null_depth_entries(dev, monkeypatch):
-    """gsr_backward_batch_ext with NULL depth entries for the views without a depth loss (views 1 and 3): those views take no depth term in
+    """gsr_backward_batch_ex with NULL depth entries for the views without a depth loss (views 1 and 3): those views take no depth term in
     the per-Gaussian backward; the result equals the sum of the single-view calls."""
     P, W, H, V = 3000, 160, 120, 4
     g = random_gaussians(P, seed=12, scale_lo=0.02, scale_hi=0.25)

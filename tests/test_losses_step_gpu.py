@@ -229,7 +229,7 @@ def test_fused_adam_equals_torch_adam(dev):
 
 
 def test_direct_step_without_host_sync_and_its_overflow_path(dev):
-    """The direct step renders in capacity mode (gsr_forward_batch_capacity: buffers sized from the previous call, entry counts
+    """The direct step renders in capacity mode (gsr_forward_batch_capacity_raw: buffers sized from the previous call, entry counts
     read on the device, no host wait in the forward).  (1) Steady state: same loss and gradients as the synchronous autograd
     step, bit for bit in the rasterizer's integers (radii) and within rounding in the floats.  (2) The scene grows by more than
     the slack between two calls: the forward overflows its buffers, the step notices before differentiating and repeats itself
