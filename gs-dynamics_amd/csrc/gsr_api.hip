@@ -974,8 +974,13 @@ int32_t gsr_shared_terms_partials(int32_t n_fg, int32_t n_bg) {
 
 static int shared_terms_check(const char* who, int32_t n_fg, int32_t K, int32_t n_bg, const void* const* ptrs, int n) {
   if (n_fg < 0 || n_bg < 0 || K <= 0) { gsr_set_error("%s: bad sizes", who); return -2; }
-  for (int i = 0; i < n; ++i)
+  // an array of n_fg (n_bg) rows may be NULL when there is no foreground (background): an empty torch tensor has no address
+  const unsigned fg_arrays = 1u << 2 | 1u << 4 | 1u << 5 | 1u << 6 | 1u << 7 | 1u << 8 | (n > 14 ? 1u << 14 : 0u);   // fg_idx, neighbour / prev arrays, rev_edge
+  const unsigned bg_arrays = 1u << 3 | 1u << 9 | 1u << 10;                                                          // bg_idx, init_bg_*
+  for (int i = 0; i < n; ++i) {
+    if ((n_fg == 0 && (fg_arrays >> i & 1u)) || (n_bg == 0 && (bg_arrays >> i & 1u))) continue;
     if (!ptrs[i]) { gsr_set_error("%s: NULL argument (#%d)", who, i); return -2; }
+  }
   return 0;
 }
 

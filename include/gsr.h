@@ -367,7 +367,8 @@ int gsr_rigidity_backward(int32_t n_fg, int32_t K, const float* means3D, const f
  *   GSR_SHARED_ACCUMULATE in `flags`, ADDED to what the buffers hold (rows in neither index list are left alone);
  *   scratch = gsr_shared_terms_scratch(n_fg, K) floats, 16-byte aligned; its first 16 n_fg floats are the per-point frames the
  *   forward left at the start of `partials`: pass that buffer (if large enough) with GSR_SHARED_FRAMES_VALID to skip their
- *   recomputation.  rev_ptr / rev_edge as for gsr_rigidity_backward. */
+ *   recomputation.  rev_ptr / rev_edge as for gsr_rigidity_backward.
+ * n_fg = 0 or n_bg = 0 is allowed: the arrays with that many rows may then be NULL, and a mean over no elements is 0 (torch: NaN). */
 #define GSR_SHARED_ACCUMULATE 1
 #define GSR_SHARED_FRAMES_VALID 2
 int32_t gsr_shared_terms_scratch(int32_t n_fg, int32_t K);

@@ -452,7 +452,7 @@ def test_fused_rigidity_terms_match_torch_autograd(dev):
     """rigid / rot / iso through gsr_rigidity.hip against the torch formulas evaluated in fp64 (values and the gradients
     w.r.t. means3D and the normalised rotations), on a scene with foreground and background Gaussians."""
     from gsdyn import synth_scene_params
-    from gsdyn.losses import build_rotation, quat_mult, rigidity_terms, weighted_l2_loss_v1, weighted_l2_loss_v2
+    from gsdyn.losses import rigidity_terms
     from gsdyn.step import make_rigidity_variables
     P = 6000
     params = synth_scene_params(P, device=dev)
@@ -464,19 +464,11 @@ def test_fused_rigidity_terms_match_torch_autograd(dev):
     a, b, c = rigidity_terms(m1, r1, variables)
     wts = (200.0, 4.0, 1000.0)
     (wts[0] * a + wts[1] * b + wts[2] * c).backward()
-    # fp64 torch reference of the same formulas
+    # fp64 torch reference of the same formulas (tests/step_ref.py)
+    from step_ref import neighbour_terms
     is_fg = params["seg_colors"][:, 0] > 0.5
     m2, r2 = means.double().clone().requires_grad_(True), rots.double().clone().requires_grad_(True)
-    fg_pts, fg_rot = m2[is_fg], r2[is_fg]
-    rel = quat_mult(fg_rot, variables["prev_inv_rot_fg"].double())
-    R = build_rotation(rel)
-    nbr = variables["neighbor_indices"]
-    off = fg_pts[nbr] - fg_pts[:, None]
-    offp = (off[:, :, :, None] * R[:, None, :, :]).sum(2)
-    nw = variables["neighbor_weight"].double()
-    ra = weighted_l2_loss_v2(offp, variables["prev_offset"].double(), nw)
-    rb = weighted_l2_loss_v2(rel[nbr], rel[:, None], nw)
-    rc = weighted_l2_loss_v1(torch.sqrt((off ** 2).sum(-1) + 1e-20), variables["neighbor_dist"].double(), nw)
+    ra, rb, rc = neighbour_terms(m2, r2, variables)
     (wts[0] * ra + wts[1] * rb + wts[2] * rc).backward()
     for got, want in ((a, ra), (b, rb), (c, rc)):
         assert abs(got.item() - want.item()) <= 2e-5 * abs(want.item()) + 1e-9
