@@ -491,6 +491,14 @@ __global__ __launch_bounds__(GSR_BLOCK) void lbs_kernel(int P, int nb, const flo
   for (int u = 0; u < LBS_PER_THREAD; ++u) {
     const int p = p0 + u * GSR_BLOCK;
     if (p >= P) continue;
+    if (nb <= 0) {        // no bone (an empty set, or *nb_valid = 0): nobody moves -- the inputs pass through, not 0 * (1 / 0)
+      out_xyz[3 * p] = x[u]; out_xyz[3 * p + 1] = y[u]; out_xyz[3 * p + 2] = z[u];
+      if (quat && out_quat) {
+        const float b0 = quat[4 * p], b1 = quat[4 * p + 1], b2 = quat[4 * p + 2], b3 = quat[4 * p + 3];
+        out_quat[4 * p] = b0; out_quat[4 * p + 1] = b1; out_quat[4 * p + 2] = b2; out_quat[4 * p + 3] = b3;
+      }
+      continue;
+    }
     const float inv = 1.0f / ws[u];
     out_xyz[3 * p] = ax[u] * inv; out_xyz[3 * p + 1] = ay[u] * inv; out_xyz[3 * p + 2] = az[u] * inv;
     if (quat && out_quat) {

@@ -1195,7 +1195,9 @@ def fit_bones(bones: torch.Tensor, motions: torch.Tensor, relations: torch.Tenso
 def linear_blend_skinning(bones, rotations, translations, bone_quats, xyz, quat, n_valid=None, in_place=False, out=None):
     """gsr_lbs: returns (xyz_new [P,3], quat_new [P,4] or None, None) -- the [P, n_bones] weight matrix of the reference is
     never materialised.  in_place: xyz / quat (float32, contiguous) are overwritten and returned.  out = (xyz_out, quat_out):
-    contiguous float32 tensors of the inputs' shapes that receive the result (a frame's slot of the episode arrays: no copy)."""
+    contiguous float32 tensors of the inputs' shapes that receive the result (a frame's slot of the episode arrays: no copy).
+    n_valid ([1] int32 on the device): only the first n_valid[0] bones are real (gsr_lbs_valid); a count above n_bones means all of
+    them, and a count of 0 means nobody moves: the result equals xyz / quat bit for bit (in place: they stay as they are)."""
     lib = load_library()
     _require_device(xyz)
     dev = xyz.device

@@ -450,7 +450,9 @@ int gsr_construct_edges(const float* positions, int32_t n_obj_cap, const int32_t
  * that ends a graphed rollout step, one launch -- pos_track[t] = all_pos[track[t]]; hist [n_his, n_track, 3] and eef_hist [n_his, 3] shifted
  * by one frame with the new positions / eef_next appended (/root/reference/src/gnn/dynamics_module.py:150-165 does this with torch.cat);
  * pred_out [n_bones, 3] = pred_in rows below *n_valid, zeros above; *n_valid_out = *n_valid; *bad += bones below *n_valid with code 1.
- * gsr_lbs / gsr_lbs_valid: out_xyz / out_quat may be xyz / quat themselves (in place). */
+ * gsr_lbs / gsr_lbs_valid: out_xyz / out_quat may be xyz / quat themselves (in place).  *n_valid above n_bones counts as n_bones.
+ * *n_valid <= 0 -- no real bone -- means NOBODY MOVES: out_xyz = xyz and out_quat = quat, bit for bit (in place: left as they are),
+ * never the 0 * (1 / 0) of an empty weight sum.  (n_bones itself must be >= 1: both calls refuse an empty bone array.) */
 int gsr_construct_edges_dense(const float* positions, int32_t n_obj_cap, const int32_t* n_valid, float thresh_sq, int32_t topk, int64_t dummy_index,
                               int32_t e_cap, int64_t* receivers, int64_t* senders, int32_t* count, int64_t* relations, int32_t relations_n,
                               void* stream);
