@@ -671,7 +671,7 @@ def test_fused_activations_in_the_direct_step(dev):
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("GSR_MV_SOAK", "12"))))
 def test_random_shapes_of_the_fused_image_loss(dev, seed):
-    """Seeded random image shapes (down to one pixel row, ragged against the kernels' 16 x 16 tiles and the 11-tap window, smooth and noisy
+    """Seeded random image shapes (down to one pixel row, ragged against the kernels' 32 x 54 tiles and the 11-tap window, smooth and noisy
     content) through the fused 0.8 L1 + 0.2 (1 - SSIM) kernels against the fp64 torch statement of the reference formula: value, gradient."""
     from gsdyn import losses as L
     rng = np.random.default_rng(2100 + seed)
