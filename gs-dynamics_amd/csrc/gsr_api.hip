@@ -909,6 +909,44 @@ int gsr_backward_batch(int32_t V, const gsr_settings* s, int32_t P, const uint32
                                dL_dcolors, dL_dcolors_views, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, nullptr, stream);
 }
 
+int gsr_sh_backward_views(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* shs,
+                          const int32_t* const* radii, void* const* geom_states,
+                          const float* const* dL_dcolors_views, float* dL_dsh, float* dL_dmeans3D, void* stream) {
+  GsrRange _range("gsr_sh_backward_views");
+  if (V <= 0 || V > GSR_MAX_BATCH) { gsr_set_error("gsr_sh_backward_views: V must be in 1..%d", GSR_MAX_BATCH); return -2; }
+  if (!s) { gsr_set_error("gsr_sh_backward_views: NULL settings"); return -2; }
+  const int deg = s[0].sh_degree, M = s[0].sh_coeffs;
+  if (deg < 0 || deg > 3 || M < (deg + 1) * (deg + 1) || M > 16) {   // (the rule of check_inputs)
+    gsr_set_error("gsr_sh_backward_views: sh_degree %d needs (deg+1)^2 <= sh_coeffs (%d) <= 16", deg, M);
+    return -2;
+  }
+  for (int v = 1; v < V; ++v)
+    if (s[v].sh_degree != deg || s[v].sh_coeffs != M) {
+      gsr_set_error("gsr_sh_backward_views: view %d's sh_degree / sh_coeffs differ from view 0's", v);
+      return -2;
+    }
+  if (P <= 0) return 0;
+  if (!means3D || !shs || !radii || !geom_states || !dL_dcolors_views || !dL_dsh || !dL_dmeans3D) {
+    gsr_set_error("gsr_sh_backward_views: NULL argument");
+    return -2;
+  }
+  GsrShViews t;
+  t.V = V; t.P = P; t.M = M; t.deg = deg;
+  t.vec4 = (((uintptr_t)shs | (uintptr_t)dL_dsh) & 15u) == 0 ? 1 : 0;
+  t.means3D = means3D; t.shs = shs; t.dL_dsh = dL_dsh; t.dL_dmeans3D = dL_dmeans3D;
+  for (int v = 0; v < V; ++v) {
+    if (!radii[v] || !geom_states[v] || !dL_dcolors_views[v] || !s[v].campos) {
+      gsr_set_error("gsr_sh_backward_views: NULL radii / geom_state / dL_dcolors_views / campos of view %d", v);
+      return -2;
+    }
+    GeomState g;
+    gsr_carve_geom(geom_states[v], P, &g);
+    t.v[v].campos = s[v].campos; t.v[v].radii = radii[v]; t.v[v].clamped = g.clamped; t.v[v].dcol = dL_dcolors_views[v];
+  }
+  for (int v = V; v < GSR_MAX_BATCH; ++v) t.v[v] = GsrShView{nullptr, nullptr, nullptr, nullptr};
+  return gsr_launch_sh_bwd_views(t, (hipStream_t)stream);
+}
+
 int32_t gsr_rigidity_blocks(int32_t n_fg) { return gsr_rigidity_fwd_blocks(n_fg); }
 
 int gsr_rigidity_forward(int32_t n_fg, int32_t K, const float* means3D, const float* rotations, const int64_t* fg_idx,

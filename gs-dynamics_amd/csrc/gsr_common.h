@@ -384,6 +384,24 @@ static inline int gsr_camera_blocks(int P, int H, int W) {
   return (int)(n > 0 ? n : 1);
 }
 int gsr_launch_camera_bwd(const GsrCamViews& cv, bool antialiasing, hipStream_t st);
+// SH colours in the multi-view call (gsr_sh_backward_views): the SH pass behind the per-Gaussian backward, which
+// was given per-view colour gradients.  One launch for every view; dL_dsh is written in full, dL_dmeans3D is accumulated into.
+struct GsrShView {
+  const float* campos;
+  const int32_t* radii;
+  const uint32_t* clamped;   // GeomState::clamped of the view's forward
+  const float* dcol;         // [P,3] this view's dL/d(rgb) (zeros where the view did not see the Gaussian)
+};
+struct GsrShViews {
+  int V, P, M, deg;
+  int vec4;                  // shs and dL_dsh are 16-byte aligned: the coalesced phases move float4
+  const float* means3D;
+  const float* shs;
+  float* dL_dsh;
+  float* dL_dmeans3D;
+  GsrShView v[GSR_MAX_BATCH];
+};
+int gsr_launch_sh_bwd_views(const GsrShViews& t, hipStream_t st);
 int gsr_launch_image_loss_fwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, float* fA,
                               float* fC, float* fE, float* block_l1, float* block_ssim, hipStream_t st);
 int gsr_launch_image_loss_bwd(const float* win11_host, int C, int H, int W, const float* x, const float* y, const float* fA,

@@ -127,14 +127,14 @@ def _camera_tensors(settings_list):
     return out
 
 
-def _camera_grads(ctx, cam_out, v):
-    """The gradients of view v's four camera arguments (apply() slots 13 + 4 v ...): each in the shape, dtype and device the caller
+def _camera_grads(ctx, cam_out, v, first=13):
+    """The gradients of view v's four camera arguments (apply() slots first + 4 v ...): each in the shape, dtype and device the caller
     passed; None where none is needed."""
     grads = []
     for k in range(4):
         shape, dtype, device = ctx.cam_meta[4 * v + k]
         g = cam_out[k] if cam_out is not None else None
-        need = ctx.needs_input_grad[13 + 4 * v + k]
+        need = ctx.needs_input_grad[first + 4 * v + k]
         grads.append(g.reshape(shape).to(dtype=dtype, device=device) if (need and g is not None) else None)
     return grads
 
@@ -217,11 +217,12 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings_list,
-                differentiable_depth=False, return_alpha=False, antialiasing=False, camera_gradients=False, *camera):
+                differentiable_depth=False, return_alpha=False, antialiasing=False, camera_gradients=False, batched_sh=False, *camera):
         ctx.set_materialize_grads(False)
         ctx.depth = bool(differentiable_depth)
         ctx.alpha = bool(return_alpha)
         # camera_gradients: `camera` = (bg, viewmatrix, projmatrix, campos) of every view in turn, the trailing apply() arguments
+        # (slots 14 ...: batched_sh sits between the switch and them)
         ctx.camera = bool(camera_gradients)
         ctx.cam_meta = [(t.shape, t.dtype, t.device) for t in camera]
         m3 = _prep(means3D)
@@ -233,7 +234,9 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         color, radii, depth, states = _hip.rasterize_forward_batch(list(settings_list), m3, op_, col_, sh_, sc_, rot_, cov_,
                                                                    prepare_backward=wants_grad, **({} if wants_grad else {"forward_only": True}),
                                                                    **({"depth_scratch": True} if (ctx.depth and wants_grad) else {}),
-                                                                   **({"antialiasing": True} if antialiasing else {}))
+                                                                   **({"antialiasing": True} if antialiasing else {}),
+                                                                   # (the batch camera pass has no SH term for campos: per view then)
+                                                                   **({"batched_sh": True} if (batched_sh and sh_ is not None and not camera_gradients) else {}))
         ctx.states = states
         _save_inputs(ctx, m3, radii, col_, sh_, sc_, rot_, cov_)
         if ctx.alpha:
@@ -249,7 +252,7 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
             grad_color = torch.zeros((V, 3, ctx.states[0].H, ctx.states[0].W), device=m3.device)
         want = None
         if ctx.camera:     # one flag per settings field: any view's tensor of that field needs a gradient
-            want = tuple(any(ctx.needs_input_grad[13 + 4 * v + k] for v in range(V)) for k in range(4))
+            want = tuple(any(ctx.needs_input_grad[14 + 4 * v + k] for v in range(V)) for k in range(4))
             if not any(want):
                 want = None
         r = _hip.rasterize_backward_batch(
@@ -262,15 +265,15 @@ class _RasterizeGaussiansViews(torch.autograd.Function):
         d3, d2, dc, do, ds, dr, dcov, dsh = r[:8]
         cam = []
         for v in range(len(ctx.cam_meta) // 4):
-            cam += _camera_grads(ctx, r[8][v] if want is not None else None, v)
+            cam += _camera_grads(ctx, r[8][v] if want is not None else None, v, 14)
         # gradients arrive already summed over views (means2D stays per view); the state stays on ctx so that a
         # second backward (retain_graph=True) works, and is released with the graph
-        return _input_grads(ctx, d3, d2, dsh, dc, do, ds, dr, dcov) + tuple(cam)
+        return _input_grads(ctx, d3, d2, dsh, dc, do, ds, dr, dcov) + (None,) + tuple(cam)
 
 
 def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
                               rotations=None, cov3D_precomp=None, differentiable_depth=False, return_alpha=False, antialiasing=False,
-                              camera_gradients=False):
+                              camera_gradients=False, batched_sh=False):
     """Render ``len(settings_list)`` views of one set of Gaussians.  ``means2D``: [V,P,3] gradient holder.
     ``differentiable_depth``: the depth output [V,1,H,W] is differentiated too (see GaussianRasterizer); views that share a camera,
     which the backward otherwise fuses into one pass, are then differentiated unfused.
@@ -279,7 +282,13 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
     densification statistic must render alpha with a separate call (its own means2D holder).
     ``antialiasing``: every view is rendered with the opacity compensation (see GaussianRasterizer).
     ``camera_gradients``: every view's bg, viewmatrix, projmatrix and campos get their gradients (see GaussianRasterizer); views that
-    share a camera, which the backward otherwise fuses into one pass, are then differentiated unfused."""
+    share a camera, which the backward otherwise fuses into one pass, are then differentiated unfused.
+    ``batched_sh`` (with ``shs``; a performance switch, not a semantic one): the views take the batch path that precomputed colours
+    take -- one launch per stage for all views, one host sync -- and one SH pass sums dL/dsh over the views, instead of one single-view
+    forward and backward per view and a stack-and-sum of V gradient sets.  The forward outputs are the per-view path's bit for bit; the
+    gradients agree with it to fp32 rounding (the multi-view per-Gaussian kernel sums in another order).  Where the batch cannot serve,
+    the per-view path runs silently: today that is ``camera_gradients=True`` (the batch camera pass has no SH term for campos).
+    Ignored with precomputed colours."""
     if (shs is None) == (colors_precomp is None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -299,7 +308,8 @@ def rasterize_gaussians_views(settings_list, means3D, means2D, opacities, shs=No
             empty if colors_precomp is None else (colors_precomp[lo:hi] if (per_view_col and not whole) else colors_precomp), opacities,
             empty if scales is None else scales, empty if rotations is None else rotations,
             empty if cov3D_precomp is None else cov3D_precomp, settings_list[lo:hi], bool(differentiable_depth), bool(return_alpha),
-            bool(antialiasing), bool(camera_gradients), *(_camera_tensors(settings_list[lo:hi]) if camera_gradients else ()))
+            bool(antialiasing), bool(camera_gradients), bool(batched_sh),
+            *(_camera_tensors(settings_list[lo:hi]) if camera_gradients else ()))
     if V <= _hip.MAX_BATCH:
         return call(0, V)
     # more views than one library call takes: several calls, outputs concatenated (autograd sums the shared inputs)

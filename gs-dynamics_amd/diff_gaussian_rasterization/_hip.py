@@ -93,7 +93,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_activate_forward", "gsr_activate_backward", "gsr_adam_step", "gsr_radius_bookkeeping", "gsr_wait_counts",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
-           "gsr_camera_scratch_bytes")
+           "gsr_camera_scratch_bytes", "gsr_sh_backward_views")
 
 
 def load_library():
@@ -139,6 +139,8 @@ def load_library():
     lib.gsr_backward_batch_ex.restype = C.c_int
     lib.gsr_backward_batch_ex.argtypes = ([i32, PS, i32, C.POINTER(u32)] + [vp] * 5 + [PV] * 4 + [vp, C.POINTER(i32), PV, PV]
                                           + [vp, PV, vp, PV, vp, vp, vp, vp, C.POINTER(GsrBackwardBatchExtras), vp])
+    lib.gsr_sh_backward_views.restype = C.c_int
+    lib.gsr_sh_backward_views.argtypes = [i32, PS, i32, vp, vp, PV, PV, PV, vp, vp, vp]
     lib.gsr_forward_batch_capacity_raw.restype = C.c_int
     lib.gsr_forward_batch_capacity_raw.argtypes = ([i32, PS, i32] + [vp] * 5 + [PV, vp, vp] + [PV, PV, PV, C.POINTER(u32), PV, vp,
                                                    C.POINTER(i32), PV, PV, vp, C.POINTER(GsrRawParams), vp])
@@ -314,12 +316,13 @@ def _dev_f32(t: torch.Tensor, dev: torch.device, n: int, name: str) -> torch.Ten
 class RasterState:
     """What forward hands to backward (the role of the reference extension's three opaque buffers)."""
     __slots__ = ("settings", "keep", "P", "num_rendered", "geom", "binning", "image", "H", "W", "pre", "batch", "geometry_of",
-                 "pending", "act", "raw_fused", "forward_only")
+                 "pending", "act", "raw_fused", "forward_only", "sh_batch")
 
     def __init__(self):
         self.forward_only = False  # batch forward with forward_only=True: the states cannot be differentiated
         self.act = None          # batch forward with raw=...: (rotations, opacities, scales) after their activations (view 0's state)
         self.raw_fused = None    # (unnorm_rotations,) when the activations ran inside the forward: the backward applies their chain too
+        self.sh_batch = False    # batch forward with shs (batched_sh=True): the backward finishes with gsr_sh_backward_views
 
 
 ANTIALIASING = 2        # GSR_SETTINGS_ANTIALIASING of include/gsr.h: bit 1 of gsr_settings.prefiltered
@@ -502,13 +505,17 @@ FORWARD_ONLY = 1        # GSR_FORWARD_ONLY of include/gsr.h
 
 def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, shs, scales, rotations, cov3D_precomp,
                             prepare_backward: bool = False, no_host_sync: bool = False, raw=None, forward_only: bool = False,
-                            grad_out=None, depth_cuts=None, depth_scratch: bool = False, antialiasing: bool = False):
+                            grad_out=None, depth_cuts=None, depth_scratch: bool = False, antialiasing: bool = False,
+                            batched_sh: bool = False):
     """All views of a step in one call: one launch per stage for all views, one host sync for all duplicate counts.  Returns (color[V,3,H,W], radii[V,P] int32, depth[V,1,H,W], states[V]).
     ``depth_cuts = (cut_in, cut_out, redo[, margin = 1.01])`` (forward_only calls; include/gsr.h: gsr_arm_depth_cuts): per view a [T] int32 tensor of depth
     bits to bin with (or None), a [T] int32 tensor that receives the next frame's proposal, and one zeroed [V] int32 tensor of redo flags.
     ``depth_scratch``: the backward that follows will take a depth gradient -- the pre-allocated scratch is sized for it
     (gsr_backward_scratch_bytes_depth).
     ``antialiasing``: GSR_SETTINGS_ANTIALIASING for every view; the states keep it for the backward.
+    ``batched_sh`` (with ``shs``): the views go through the count-first batch path like precomputed colours do
+    -- the preprocess evaluates the SH colours per view -- instead of one single-view forward each; rasterize_backward_batch then
+    finishes with gsr_sh_backward_views.  Views that share a camera share nothing here, and there is no capacity mode.
     ``raw = (unnorm_rotations, logit_opacities, log_scales)`` (then ``opacities`` / ``scales`` / ``rotations`` are None): the
     activations are applied inside the preprocess kernel when the call runs in capacity mode (``states[0].raw_fused``), by
     ``activate_forward`` otherwise; either way ``states[0].act = (rotations, opacities, scales)`` holds the activated tensors."""
@@ -532,7 +539,7 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
     if any(int(rs.image_height) != H or int(rs.image_width) != W for rs in settings_list):
         raise ValueError("rasterize_forward_batch: all views must share the image size")
     M = 0 if shs is None else int(shs.shape[1])
-    if shs is not None:
+    if shs is not None and not batched_sh:
         # SH colours depend on the camera position, and the multi-view backward kernel covers precomputed colours only: every
         # view takes the single-view entry points, so that each state owns the tile order / queue / binning that
         # gsr_backward reads (the batch state of a multi-view call keeps them in one shared table instead).
@@ -566,7 +573,7 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
             k = (id(rs.viewmatrix), id(rs.projmatrix), id(rs.campos), float(rs.tanfovx), float(rs.tanfovy),
                  float(rs.scale_modifier), bool(rs.prefiltered))
             geo.append(first.setdefault(k, v))
-        geometry_of = (C.c_int32 * V)(*geo) if any(g != v for v, g in enumerate(geo)) else None
+        geometry_of = (C.c_int32 * V)(*geo) if (shs is None and any(g != v for v, g in enumerate(geo))) else None
         owner = [geometry_of is None or geo[v] == v for v in range(V)]
         cap_e = _entries_capacity.get(key, 0) if (no_host_sync and shs is None and P > 0) else 0
         if cap_e:
@@ -702,6 +709,7 @@ def rasterize_forward_batch(settings_list, means3D, opacities, colors_precomp, s
         state.pending = None
         state.act = act if v == 0 else None
         state.forward_only = bool(forward_only)
+        state.sh_batch = shs is not None
         states.append(state)
     return color, radii, depth, states
 
@@ -771,7 +779,10 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     ``grad_alpha`` (same forms): the rendered alphas' gradient (fused pairs stay fused; a None entry = no alpha gradient for that view).
     None, or no image at all, for both is exactly gsr_backward_batch.
     ``camera_grads`` (see rasterize_backward; the same flags for every view): the camera pass (fused pairs run unfused), and an
-    eighth element, a list of V tuples (d_bg, d_viewmatrix, d_projmatrix, d_campos).  SH colours: the single-view path's."""
+    eighth element, a list of V tuples (d_bg, d_viewmatrix, d_projmatrix, d_campos).  SH colours: the single-view path's.
+    SH colours over the states of a batch forward (``rasterize_forward_batch(..., batched_sh=True)``): the batch backward writes every
+    view's dL/d(rgb), gsr_sh_backward_views turns them into ``dsh`` [P,M,3] and adds the view-direction term to ``dmeans3D``;
+    ``camera_grads`` is rejected there (the batch camera pass has no SH term for campos)."""
     lib = load_library()
     dev = means3D.device
     V = len(states)
@@ -782,7 +793,10 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
     f32 = dict(dtype=torch.float32, device=dev)
     gd = None if grad_depth is None else _view_images(grad_depth, states, "grad_depth", f32)
     ga = None if grad_alpha is None else _view_images(grad_alpha, states, "grad_alpha", f32)
-    if shs is not None:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
+    sh_batch = shs is not None and states[0].sh_batch    # the states of a batched_sh forward
+    if sh_batch and want is not None:
+        raise RuntimeError("rasterize_backward_batch: camera_grads with SH colours needs the per-view forward (batched_sh=False)")
+    if shs is not None and not sh_batch:  # SH colours: per-view backward + sum (the fused multi-view kernel covers precomputed colours)
         outs = [rasterize_backward(states[v], grad_color[v], means3D, radii[v], None, shs, scales, rotations, cov3D_precomp,
                                    grad_depth=None if gd is None else gd[v], grad_alpha=None if ga is None else ga[v],
                                    **({} if want is None else {"camera_grads": want}))
@@ -801,7 +815,9 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
         for v, stt in enumerate(states):
             sarr[v] = stt.settings
             Ds[v] = stt.num_rendered
-        per_view_col = colors_precomp is not None and colors_precomp.dim() == 3
+        # (SH: every view's dL/d(rgb) [P,3] is the SH pass's input, wanted whatever the caller said about colour gradients)
+        per_view_col = sh_batch or (colors_precomp is not None and colors_precomp.dim() == 3)
+        want_color_grad = want_color_grad or sh_batch
         pre, states[0].pre = states[0].pre, None   # one use only: autograd may keep the returned tensors as .grad
         # the depth build's scratch: the records, then one float of dL/dz per entry (a forward told so -- depth_scratch -- sized it already)
         sbytes = lib.gsr_backward_scratch_bytes_depth if gd is not None else lib.gsr_backward_scratch_bytes
@@ -844,6 +860,12 @@ def rasterize_backward_batch(states, grad_color, means3D, radii, colors_precomp,
             ex.cams, ex.cam_scratch = C.addressof(recs), _ptr(cam_scratch)
         rc = lib.gsr_backward_batch_ex(*args, *plain, _ptr(d_cov), C.byref(ex), _stream(dev))
         _check(rc, "gsr_backward_batch")
+        if sh_batch:     # the SH pass: dL/dsh summed over the views, and += the view-direction term into the freshly written d_means3D
+            shs_c = shs.to(**f32).contiguous()
+            d_sh = torch.empty(tuple(shs_c.shape), **f32)
+            _check(lib.gsr_sh_backward_views(V, sarr, P, _ptr(means3D), _ptr(shs_c), per_view(radii), _ptr_array([stt.geom for stt in states]),
+                                             per_view(d_colors), _ptr(d_sh), _ptr(d_means3D), _stream(dev)), "gsr_sh_backward_views")
+            return (d_means3D, d_means2D, None, d_opacity, d_scales, d_rot, d_cov, d_sh)
     # without a colour gradient, views that share a camera stay fused in the backward (one replay of the tile lists for both)
     res = (d_means3D, d_means2D, (d_colors if want_color_grad else None), d_opacity, d_scales, d_rot, d_cov, None)
     return res if want is None else res + (cam_out,)

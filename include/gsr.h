@@ -302,7 +302,8 @@ int gsr_forward_batch_capacity_raw(int32_t V, const gsr_settings* s, int32_t P, 
                                    const uint32_t* capacity_entries, void* const* image_states, void* batch_state,
                                    const int32_t* geometry_of, float* const* out_color, float* const* out_depth,
                                    uint32_t* counts_dev, const gsr_raw_params* raw, void* stream);
-/* Backward of all V views (precomputed colours only; with SH use gsr_backward per view): ONE blend-backward launch
+/* Backward of all V views (precomputed colours; after an SH batch forward, pass dL_dcolors_views and complete the call with
+ * gsr_sh_backward_views below -- or differentiate each view with gsr_backward): ONE blend-backward launch
  * over the combined tile queue, then ONE per-Gaussian kernel that loops over the views and writes the
  * gradients SUMMED over views.  Only dL_dmeans2D stays per view ([V] pointers to [P,3]).  It is gsr_backward_batch_ex (below) with
  * ex == NULL. */
@@ -341,6 +342,20 @@ int gsr_backward_batch_ex(int32_t V, const gsr_settings* s, int32_t P, const uin
                           float* const* dL_dmeans2D, float* dL_dcolors, float* const* dL_dcolors_views, float* dL_dopacity,
                           float* dL_dscales, float* dL_drotations, float* dL_dcov3D, const gsr_backward_batch_extras* ex,
                           void* stream);
+/* SH colours in the multi-view call: the SH pass of all V views in one launch.  It COMPLETES a gsr_backward_batch_ex call that was given
+ * dL_dcolors_views (colors_precomp = NULL, dL_dcolors = NULL) after a batch forward with `shs` (gsr_forward_batch, or the two-stage
+ * pair): that call leaves each view's dL/d(rgb) [P,3], and this one turns them into
+ *   dL_dsh [P, sh_coeffs, 3]  WRITTEN in full: the sum over the views in ascending view order; coefficients beyond (sh_degree + 1)^2 and
+ *                             the rows of Gaussians no view saw (radii <= 0 everywhere) are exactly 0;
+ *   dL_dmeans3D [P,3]         ACCUMULATED INTO, not overwritten: += the views' gradient through the view direction p - campos.  Pass the
+ *                             array the batch backward wrote, on the same stream (a NaN it left there stays a NaN).
+ * geom_states and radii must be those of that forward (the states hold each view's clamp bits), `s` its settings, `shs` its coefficients
+ * and dL_dcolors_views [V] the pointers the batch backward was given.  No atomics: results are bit-identical from run to run.
+ * Returns -2 (with a message) for NULL settings, a NULL table or entry, V outside 1..GSR_MAX_BATCH, or sh_degree / sh_coeffs that are
+ * inconsistent ((sh_degree + 1)^2 <= sh_coeffs <= 16, sh_degree in 0..3) or differ between the views; P <= 0 returns 0 without a launch. */
+int gsr_sh_backward_views(int32_t V, const gsr_settings* s, int32_t P, const float* means3D, const float* shs,
+                          const int32_t* const* radii, void* const* geom_states,
+                          const float* const* dL_dcolors_views, float* dL_dsh, float* dL_dmeans3D, void* stream);
 /* ---- neighbour terms of the t > 0 tracking loss, fused (caller side of the path):
  *   rigid, rot, iso of /root/reference/src/tracking/train_utils.py:198-222 as three means over (foreground point, neighbour).
  * All per-point arrays are indexed by foreground rank; fg_idx[n_fg] (int64) maps rank -> Gaussian; neighbor_* are [n_fg,K];
