@@ -93,7 +93,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_activate_forward", "gsr_activate_backward", "gsr_adam_step", "gsr_radius_bookkeeping", "gsr_wait_counts",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
-           "gsr_camera_scratch_bytes", "gsr_sh_backward_views")
+           "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
+           "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail")
 
 
 def load_library():
@@ -217,6 +218,12 @@ def load_library():
     lib.gsr_arm_depth_cuts.argtypes = [i32, vp, vp, vp, C.c_float]
     lib.gsr_rollout_step_motion.restype = C.c_int
     lib.gsr_rollout_step_motion.argtypes = [i32, i32, C.c_float, vp, vp, vp, vp, vp]
+    lib.gsr_construct_edges_batch.restype = C.c_int
+    lib.gsr_construct_edges_batch.argtypes = [i32, vp, i32, vp, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.gsr_plan_step_head.restype = C.c_int
+    lib.gsr_plan_step_head.argtypes = [i32] * 5 + [vp] * 10
+    lib.gsr_plan_step_tail.restype = C.c_int
+    lib.gsr_plan_step_tail.argtypes = [i32] * 6 + [C.c_float] + [vp] * 7
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1131,6 +1138,82 @@ def rollout_step_tail(all_pos, track, pos_track, hist, eef_hist, eef_next, pred_
         _check(lib.gsr_rollout_step_tail(int(track.shape[0]), int(hist.shape[0]), int(pred_out.shape[0]), _ptr(all_pos), _ptr(track), _ptr(pos_track),
                                          _ptr(hist), _ptr(eef_hist), _ptr(eef_next), _ptr(pred_in), _ptr(n_valid), _ptr(code), _ptr(pred_out),
                                          _ptr(n_valid_out), _ptr(bad), _stream(dev)), "gsr_rollout_step_tail")
+
+
+def plan_edge_capacity(B: int, n_obj: int, topk: int) -> int:
+    """The exact upper bound of gsr_construct_edges_batch's list: per sample n_obj min(topk, n_obj) object relations and 2 n_obj with the tool."""
+    return int(B) * (int(n_obj) * min(int(topk), int(n_obj)) + 2 * int(n_obj))
+
+
+def construct_edges_batch(pos: torch.Tensor, n_valid: torch.Tensor, thresh: float, topk: int, e_cap: Optional[int] = None):
+    """gsr_construct_edges_batch (include/gsr.h): pos [B, n_obj_cap + 1, 3] (each sample's tool last), n_valid [1] int32 on the device ->
+    (receivers [e_cap], senders [e_cap] int64 in GLOBAL rows b R + i, padded with B R; count [1] int32; row_start [B R + 2] int64).
+    e_cap defaults to the exact bound ``plan_edge_capacity``; a smaller one is refused (RuntimeError, nothing launched)."""
+    import numpy as np
+    lib = load_library()
+    _require_device(pos)
+    dev = pos.device
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise ValueError("construct_edges_batch: positions must be [B, n_obj_cap + 1, 3]")
+    if not (n_valid.dtype == torch.int32 and n_valid.device == dev and n_valid.is_contiguous() and n_valid.numel() >= 1):
+        raise ValueError("construct_edges_batch: n_valid must be a contiguous int32 tensor on the positions' device")
+    B, R = int(pos.shape[0]), int(pos.shape[1])
+    if e_cap is None:
+        e_cap = plan_edge_capacity(B, R - 1, topk)
+    e_cap = int(e_cap)
+    with _on(dev):
+        p = pos.to(torch.float32).contiguous()
+        recv = torch.empty((max(e_cap, 0),), dtype=torch.int64, device=dev)
+        send = torch.empty((max(e_cap, 0),), dtype=torch.int64, device=dev)
+        cnt = torch.empty((1,), dtype=torch.int32, device=dev)
+        rows = torch.empty((B * R + 2,), dtype=torch.int64, device=dev)
+        scratch = torch.empty((max(B, 1) * (2 * R + 1),), dtype=torch.int64, device=dev)
+        thr2 = float(np.float32(float(thresh) * float(thresh)))          # the scalar a float32 tensor is compared with
+        _check(lib.gsr_construct_edges_batch(B, _ptr(p), R - 1, _ptr(n_valid), thr2, int(topk), e_cap, _ptr(recv), _ptr(send), _ptr(cnt), _ptr(rows),
+                                             _ptr(scratch), _stream(dev)), "gsr_construct_edges_batch")
+    return recv, send, cnt, rows
+
+
+def plan_step_head(hist, eef_hist, eef_delta, attrs, instance, with_state: bool):
+    """gsr_plan_step_head (include/gsr.h): hist [B, n_his, n_obj, 3], eef_hist [B, n_his, 3], eef_delta [B, 3], attrs [B R + 1, A], instance
+    [B R + 1] (R = n_obj + 1) -> (state_rows [B R + 1, 3 n_his], particle_inputs, rel_nodes, states_last [B, R, 3]), one launch."""
+    lib = load_library()
+    _require_device(hist)
+    dev = hist.device
+    B, n_his, n_obj = int(hist.shape[0]), int(hist.shape[1]), int(hist.shape[2])
+    n_rows, A = B * (n_obj + 1) + 1, int(attrs.shape[1])
+    for t in (hist, eef_hist, eef_delta, attrs, instance):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev):
+            raise ValueError("plan_step_head: contiguous float32 tensors on one device, please")
+    if (tuple(eef_hist.shape) != (B, n_his, 3) or tuple(eef_delta.shape) != (B, 3) or int(attrs.shape[0]) != n_rows or int(instance.numel()) != n_rows
+            or hist.shape[3] != 3):
+        raise ValueError("plan_step_head: shapes do not fit hist [B, n_his, n_obj, 3]")
+    with _on(dev):
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
+        st, p_in, nodes = e(n_rows, 3 * n_his), e(n_rows, A + (3 * n_his if with_state else 0) + 3), e(n_rows, A + 1 + 3 * n_his)
+        last = e(B, n_obj + 1, 3)
+        _check(lib.gsr_plan_step_head(B, n_his, n_obj, A, 1 if with_state else 0, _ptr(hist), _ptr(eef_hist), _ptr(eef_delta), _ptr(attrs), _ptr(instance),
+                                      _ptr(st), _ptr(p_in), _ptr(nodes), _ptr(last), _stream(dev)), "gsr_plan_step_head")
+    return st, p_in, nodes, last
+
+
+def plan_step_tail(pred_motion, eef_delta, repeat, hist, eef_hist, out_seq, ai: int, li: int, motion_clamp: float):
+    """gsr_plan_step_tail (include/gsr.h): pred_motion [>= B R, 3], eef_delta [B, 3], repeat [B, T] int32; hist [B, n_his, n_obj, 3] and eef_hist
+    [B, n_his, 3] are advanced IN PLACE, out_seq [B, T, n_obj, 3] receives the rows of the samples with repeat[b, li] == ai."""
+    lib = load_library()
+    _require_device(hist)
+    dev = hist.device
+    B, n_his, n_obj, T = int(hist.shape[0]), int(hist.shape[1]), int(hist.shape[2]), int(out_seq.shape[1])
+    for t in (pred_motion, eef_delta, hist, eef_hist, out_seq):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev):
+            raise ValueError("plan_step_tail: contiguous float32 tensors on one device, please")
+    if (not (repeat.is_contiguous() and repeat.dtype == torch.int32 and repeat.device == dev) or tuple(repeat.shape) != (B, T)
+            or tuple(out_seq.shape) != (B, T, n_obj, 3) or tuple(eef_hist.shape) != (B, n_his, 3) or tuple(eef_delta.shape) != (B, 3)
+            or pred_motion.dim() != 2 or pred_motion.shape[1] != 3 or int(pred_motion.shape[0]) < B * (n_obj + 1)):
+        raise ValueError("plan_step_tail: shapes do not fit hist [B, n_his, n_obj, 3] (repeat: contiguous int32 [B, T])")
+    with _on(dev):
+        _check(lib.gsr_plan_step_tail(B, n_his, n_obj, T, int(ai), int(li), float(motion_clamp), _ptr(pred_motion), _ptr(eef_delta), _ptr(repeat),
+                                      _ptr(hist), _ptr(eef_hist), _ptr(out_seq), _stream(dev)), "gsr_plan_step_tail")
 
 
 def fps_thin(pos: torch.Tensor, npoints: int, radius: float, start_idx: int = 0, thin_start_idx: int = 0):

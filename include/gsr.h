@@ -526,6 +526,33 @@ int gsr_gnn_aggregate(int32_t n_rows, int32_t n_sum_rows, int32_t width, const f
  * propagator's addend of the step (particle_encode @ Wp1^T + b, plus the effect as the residual) -- one launch less per propagation step. */
 int gsr_gnn_aggregate_res(int32_t n_rows, int32_t n_sum_rows, int32_t width, const float* rel_part, const float* node_parts, const int64_t* senders,
                           const int64_t* row_start, float* agg, const float* res_a, const float* res_b, float* res_out, void* stream);
+/* ---- the planner's rollout (gsdyn/plan.py; /root/reference/src/real_world/plan.py:24-154): B action samples advance B copies of one particle
+ * state through the propagation network in ONE batch.  Sample b owns the global rows b R .. b R + R - 1 (R = n_obj + 1: the object
+ * particles, then the one tool particle at b R + n_obj); row B R is a dummy row behind the last sample that collects the padding.  To
+ * gsr_gnn_rel_inputs / gsr_gnn_aggregate the B graphs are one graph with B R + 1 rows.  Additive to ABI 125 (no existing symbol changed).
+ * gsr_construct_edges_batch: positions [B, R, 3], *n_valid (device, shared by all samples) real objects per sample; per sample the rule of
+ *   gsr_construct_edges (both ends real, not both tools, (dx dx + dy dy) + dz dz < thresh_sq, among objects the sender one of the
+ *   receiver's min(topk, 16, *n_valid) nearest, itself included, ties to the lower index).  receivers / senders [e_cap]: the compact list in
+ *   GLOBAL row indices, in sample order and row-major within a sample (ascending in the receiver), padded with B R in both; *count = the
+ *   real entries; row_start [B R + 2]: row_start[r] = entries whose receiver is below r, row_start[B R] = *count, row_start[B R + 1] = e_cap.
+ *   e_cap must be at least B (n_obj_cap min(topk, n_obj_cap) + 2 n_obj_cap), the exact upper bound, so nothing is ever truncated (-3 and
+ *   no launch otherwise).  scratch: B (2 R + 1) 64-bit words.  Two launches, no atomics, bit-identical from run to run.
+ * gsr_plan_step_head: hist [B, n_his, n_obj, 3], eef_hist [B, n_his, 3], eef_delta [B, 3], attrs [B R + 1, attr_dim] and instance [B R + 1]
+ *   (constant per-row inputs; the dummy row's are zero) -> state_rows [B R + 1, 3 n_his], particle_inputs [B R + 1, attr_dim + (with_state ?
+ *   3 n_his : 0) + 3] = (attributes, [state], action: the tool row's eef_delta, zeros elsewhere), rel_nodes [B R + 1, attr_dim + 1 + 3 n_his]
+ *   = (attributes, instance, state) -- gsr_rollout_step_head's layouts -- and states_last [B, R, 3]; the dummy row's state is zero.
+ * gsr_plan_step_tail: pred_motion [>= B R rows, 3] (the network's output for the global rows) -> predicted = last + clamp(motion,
+ *   +-motion_clamp) for the object rows; the tool's new position = (last tool x, y + eef_delta x, y; the minimum predicted z of the sample's
+ *   objects, a NaN kept); hist and eef_hist shifted by one frame IN PLACE with the new positions appended; out_seq [B, T, n_obj, 3]:
+ *   out_seq[b, li] = predicted for the samples with repeat[b, li] == ai (repeat [B, T] int32 on the device).  n_obj <= 127. */
+int gsr_construct_edges_batch(int32_t B, const float* positions, int32_t n_obj_cap, const int32_t* n_valid, float thresh_sq, int32_t topk,
+                              int32_t e_cap, int64_t* receivers, int64_t* senders, int32_t* count, int64_t* row_start, uint64_t* scratch,
+                              void* stream);
+int gsr_plan_step_head(int32_t B, int32_t n_his, int32_t n_obj, int32_t attr_dim, int32_t with_state, const float* hist, const float* eef_hist,
+                       const float* eef_delta, const float* attrs, const float* instance, float* state_rows, float* particle_inputs, float* rel_nodes,
+                       float* states_last, void* stream);
+int gsr_plan_step_tail(int32_t B, int32_t n_his, int32_t n_obj, int32_t T, int32_t ai, int32_t li, float motion_clamp, const float* pred_motion,
+                       const float* eef_delta, const int32_t* repeat, float* hist, float* eef_hist, float* out_seq, void* stream);
 int gsr_fps(int32_t N, const float* pos, int32_t npoints, int32_t start_idx, float* scratch, int64_t* out_idx, void* stream);
 int gsr_lbs(int32_t P, int32_t n_bones, const float* bones, const float* rotations, const float* translations,
             const float* bone_quats, const float* xyz, const float* quat, float* out_xyz, float* out_quat, void* stream);
