@@ -94,7 +94,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
            "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
-           "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail")
+           "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update")
 
 
 def load_library():
@@ -224,6 +224,10 @@ def load_library():
     lib.gsr_plan_step_head.argtypes = [i32] * 5 + [vp] * 10
     lib.gsr_plan_step_tail.restype = C.c_int
     lib.gsr_plan_step_tail.argtypes = [i32] * 6 + [C.c_float] + [vp] * 7
+    lib.gsr_plan_cost.restype = C.c_int
+    lib.gsr_plan_cost.argtypes = [i32] * 4 + [vp] * 5 + [C.c_float] * 3 + [vp] * 5
+    lib.gsr_plan_mppi_update.restype = C.c_int
+    lib.gsr_plan_mppi_update.argtypes = [i32, i32, vp, vp, C.c_float, C.c_float] + [vp] * 6
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1214,6 +1218,52 @@ def plan_step_tail(pred_motion, eef_delta, repeat, hist, eef_hist, out_seq, ai: 
     with _on(dev):
         _check(lib.gsr_plan_step_tail(B, n_his, n_obj, T, int(ai), int(li), float(motion_clamp), _ptr(pred_motion), _ptr(eef_delta), _ptr(repeat),
                                       _ptr(hist), _ptr(eef_hist), _ptr(out_seq), _stream(dev)), "gsr_plan_step_tail")
+
+
+def plan_cost(state_seqs, actions, state_cur, target, box, pusher_size: float = 0.01, sharpness: float = 100.0, penalty_weight: float = 5.0):
+    """gsr_plan_cost (include/gsr.h): state_seqs [B, T, n_obj, 3], actions [B, T, 4], state_cur [n_obj, 3], target [M, 3], box [4] = (x_lo, x_hi,
+    y_lo, y_hi) -> (reward [B], chamfer [B], collision [B, T], box_pen [B, T]), one launch, no host read."""
+    lib = load_library()
+    _require_device(state_seqs)
+    dev = state_seqs.device
+    for t in (state_seqs, actions, state_cur, target, box):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev):
+            raise ValueError("plan_cost: contiguous float32 tensors on one device, please")
+    if state_seqs.dim() != 4 or state_seqs.shape[3] != 3:
+        raise ValueError("plan_cost: state_seqs must be [B, T, n_obj, 3]")
+    B, T, n_obj = int(state_seqs.shape[0]), int(state_seqs.shape[1]), int(state_seqs.shape[2])
+    if (tuple(actions.shape) != (B, T, 4) or tuple(state_cur.shape) != (n_obj, 3) or target.dim() != 2 or target.shape[1] != 3 or int(box.numel()) != 4):
+        raise ValueError("plan_cost: shapes do not fit state_seqs [B, T, n_obj, 3] (actions [B, T, 4], state_cur [n_obj, 3], target [M, 3], box [4])")
+    with _on(dev):
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
+        reward, chamfer, coll, boxp = e(B), e(B), e(B, T), e(B, T)
+        _check(lib.gsr_plan_cost(B, T, n_obj, int(target.shape[0]), _ptr(state_seqs), _ptr(actions), _ptr(state_cur), _ptr(target), _ptr(box),
+                                 float(pusher_size), float(sharpness), float(penalty_weight), _ptr(reward), _ptr(chamfer), _ptr(coll), _ptr(boxp),
+                                 _stream(dev)), "gsr_plan_cost")
+    return reward, chamfer, coll, boxp
+
+
+def plan_mppi_update(act_seqs, rewards, reward_weight: float, push_length: float, lower, upper):
+    """gsr_plan_mppi_update (include/gsr.h): act_seqs [B, T, 4], rewards [B], lower / upper [4] -> (act_seq [T, 4], best_index [1] int64,
+    best_reward [1]), one launch, no host read."""
+    lib = load_library()
+    _require_device(act_seqs)
+    dev = act_seqs.device
+    for t in (act_seqs, rewards, lower, upper):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev):
+            raise ValueError("plan_mppi_update: contiguous float32 tensors on one device, please")
+    if act_seqs.dim() != 3 or act_seqs.shape[2] != 4:
+        raise ValueError("plan_mppi_update: act_seqs must be [B, T, 4]")
+    B, T = int(act_seqs.shape[0]), int(act_seqs.shape[1])
+    if tuple(rewards.shape) != (B,) or int(lower.numel()) != 4 or int(upper.numel()) != 4:
+        raise ValueError("plan_mppi_update: shapes do not fit act_seqs [B, T, 4] (rewards [B], lower [4], upper [4])")
+    with _on(dev):
+        act_seq = torch.empty((T, 4), dtype=torch.float32, device=dev)
+        best_index = torch.empty((1,), dtype=torch.int64, device=dev)
+        best_reward = torch.empty((1,), dtype=torch.float32, device=dev)
+        _check(lib.gsr_plan_mppi_update(B, T, _ptr(act_seqs), _ptr(rewards), float(reward_weight), float(push_length), _ptr(lower), _ptr(upper),
+                                        _ptr(act_seq), _ptr(best_index), _ptr(best_reward), _stream(dev)), "gsr_plan_mppi_update")
+    return act_seq, best_index, best_reward
 
 
 def fps_thin(pos: torch.Tensor, npoints: int, radius: float, start_idx: int = 0, thin_start_idx: int = 0):

@@ -553,6 +553,31 @@ int gsr_plan_step_head(int32_t B, int32_t n_his, int32_t n_obj, int32_t attr_dim
                        float* states_last, void* stream);
 int gsr_plan_step_tail(int32_t B, int32_t n_his, int32_t n_obj, int32_t T, int32_t ai, int32_t li, float motion_clamp, const float* pred_motion,
                        const float* eef_delta, const int32_t* repeat, float* hist, float* eef_hist, float* out_seq, void* stream);
+/* ---- the planner's cost and MPPI update (gsdyn/plan.py; the reference's real_world/plan.py `running_cost` and utils/plan_utils.py
+ * `optimize_action_mppi`): the two reductions behind the rollout, one launch each.  Additive to ABI 125 (no existing symbol changed).  No
+ * atomics; every float sum runs in a fixed order (csrc/gsr_plan_cost.hip), so the outputs are bit-identical from run to run and a sample's
+ * cost depends neither on B nor on its position in the batch.  Minima and maxima keep a NaN (torch.min): a diverged sample's reward is NaN.
+ * gsr_plan_cost: state_seqs [B, T, n_obj, 3], actions [B, T, 4] (columns 0, 1 -- the push's start point -- are read), state_cur [n_obj, 3],
+ *   target [M, 3], box [4] = (x_lo, x_hi, y_lo, y_hi) ON THE DEVICE -> reward [B], chamfer [B], collision [B, T], box_pen [B, T]:
+ *   chamfer[b]      = mean_m min_n |target_m - P_n| + mean_n min_m |target_m - P_n|, P = state_seqs[b, T - 1] (minimum of the squares, then the root);
+ *   collision[b, t] = exp(-sharpness max(min_n |(x, y)_start[b, t] - Q_n| - pusher_size, 0)), Q = the xy of state_cur (t = 0), of state_seqs[b, t - 1] (t > 0);
+ *   box_pen[b, t]   = max over the four walls of exp(-sharpness max(margin, 0)), margins xmin - x_lo, x_hi - xmax, ymin - y_lo, y_hi - ymax
+ *                     of state_seqs[b, t]'s particles: 1 at or beyond a wall (the reference's rule);
+ *   reward[b]       = -chamfer[b] - penalty_weight mean_t collision[b, t] - penalty_weight mean_t box_pen[b, t].
+ *   The reference's constants: pusher_size 0.01, sharpness 100, penalty_weight 5.  B, T, M >= 1, 1 <= n_obj <= 1024, B T n_obj 3 and M 3
+ *   below 2^31, no NULL pointer: -2 and no launch otherwise.
+ * gsr_plan_mppi_update: act_seqs [B, T, 4] = (x, y, theta, length), rewards [B], lower [4] / upper [4] ON THE DEVICE -> act_seq [T, 4],
+ *   *best_index (int64), *best_reward.  best_index = the LOWEST b whose reward is the maximum, where a NaN reward counts as the maximum
+ *   (torch.argmax); best_reward = rewards[best_index].  Weights w_b = exp(reward_weight (r_b - best_reward)) / their sum (-inf: weight 0; a
+ *   NaN reward makes act_seq NaN); per step x = sum w x, y = sum w y, (dx, dy) = sum w length push_length (cos theta, sin theta) -- the
+ *   displacement summed directly, not as the difference of two summed end points --, theta = atan2(dy, dx), length = hypot(dx, dy) /
+ *   push_length; then the reference's clip: column 0 (x) through ((v + pi) mod 2 pi) - pi, every column clamped to [lower, upper].
+ *   B, T >= 1, B T 4 below 2^31, no NULL pointer: -2 and no launch otherwise. */
+int gsr_plan_cost(int32_t B, int32_t T, int32_t n_obj, int32_t M, const float* state_seqs, const float* actions, const float* state_cur,
+                  const float* target, const float* box, float pusher_size, float sharpness, float penalty_weight, float* reward, float* chamfer,
+                  float* collision, float* box_pen, void* stream);
+int gsr_plan_mppi_update(int32_t B, int32_t T, const float* act_seqs, const float* rewards, float reward_weight, float push_length, const float* lower,
+                         const float* upper, float* act_seq, int64_t* best_index, float* best_reward, void* stream);
 int gsr_fps(int32_t N, const float* pos, int32_t npoints, int32_t start_idx, float* scratch, int64_t* out_idx, void* stream);
 int gsr_lbs(int32_t P, int32_t n_bones, const float* bones, const float* rotations, const float* translations,
             const float* bone_quats, const float* xyz, const float* quat, float* out_xyz, float* out_quat, void* stream);
