@@ -94,7 +94,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_gnn_aggregate", "gsr_gnn_rel_inputs", "gsr_construct_edges_dense", "gsr_rollout_step_tail",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
            "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
-           "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update")
+           "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update",
+           "gsr_knn_scratch_bytes", "gsr_knn")
 
 
 def load_library():
@@ -228,6 +229,9 @@ def load_library():
     lib.gsr_plan_cost.argtypes = [i32] * 4 + [vp] * 5 + [C.c_float] * 3 + [vp] * 5
     lib.gsr_plan_mppi_update.restype = C.c_int
     lib.gsr_plan_mppi_update.argtypes = [i32, i32, vp, vp, C.c_float, C.c_float] + [vp] * 6
+    lib.gsr_knn_scratch_bytes.restype = sz; lib.gsr_knn_scratch_bytes.argtypes = [i32]
+    lib.gsr_knn.restype = C.c_int
+    lib.gsr_knn.argtypes = [i32, vp, i32, i32, vp, vp, vp, vp]
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1264,6 +1268,42 @@ def plan_mppi_update(act_seqs, rewards, reward_weight: float, push_length: float
         _check(lib.gsr_plan_mppi_update(B, T, _ptr(act_seqs), _ptr(rewards), float(reward_weight), float(push_length), _ptr(lower), _ptr(upper),
                                         _ptr(act_seq), _ptr(best_index), _ptr(best_reward), _stream(dev)), "gsr_plan_mppi_update")
     return act_seq, best_index, best_reward
+
+
+KNN_BRUTE_N = 2048    # csrc/gsr_knn.hip KNN_BRUTE_N: up to this many points every query takes the brute-force kernel
+KNN_MAX_SHELLS = 3    # csrc/gsr_knn.hip KNN_MAXR
+
+
+def knn(points: torch.Tensor, k: int, exclude_self: bool = False, stats: bool = False):
+    """gsr_knn (include/gsr.h): points [N, 3] -> (idx [N, k] int64, d2 [N, k] fp32), the k nearest of every point under the total order
+    (d2 ascending, index ascending).  No host read-back.  ``stats=True`` (tools/knn_cost.py) adds a dict read from the call's scratch
+    -- that one synchronises: brute_share, mean_shells, cells (per axis), occupied cells, cell size h, points per occupied cell."""
+    lib = load_library()
+    _require_device(points)
+    dev = points.device
+    if not (points.is_contiguous() and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3):
+        raise ValueError("knn: a contiguous float32 [N, 3] tensor, please")
+    N, k = int(points.shape[0]), int(k)
+    with _on(dev):
+        scratch = torch.empty((int(lib.gsr_knn_scratch_bytes(N)) + 256,), dtype=torch.uint8, device=dev)
+        pad = (-scratch.data_ptr()) % 256
+        idx = torch.empty((N, k), dtype=torch.int64, device=dev)
+        d2 = torch.empty((N, k), dtype=torch.float32, device=dev)
+        _check(lib.gsr_knn(N, _ptr(points), k, 1 if exclude_self else 0, C.c_void_p(scratch.data_ptr() + pad), _ptr(idx), _ptr(d2), _stream(dev)),
+               "gsr_knn")
+        if not stats:
+            return idx, d2
+        if N <= KNN_BRUTE_N:
+            return idx, d2, dict(brute_share=1.0, mean_shells=0.0, cells=(0, 0, 0), occupied=0, h=0.0, per_cell=0.0)
+        hdr = scratch[pad:pad + 64].cpu()
+        info = scratch[pad + 256:pad + 256 + 4 * N].view(torch.int32)
+        g = hdr[16:28].view(torch.int32).tolist()
+        occupied = int(hdr[60:64].view(torch.int32).item())
+        grid_rows = info >= 0
+        st = dict(brute_share=float((~grid_rows).float().mean().item()),
+                  mean_shells=float((info & 0xff)[grid_rows].float().mean().item()) if bool(grid_rows.any()) else float(KNN_MAX_SHELLS),
+                  cells=tuple(g), occupied=occupied, h=float(hdr[48:52].view(torch.float32).item()), per_cell=N / max(occupied, 1))
+    return idx, d2, st
 
 
 def fps_thin(pos: torch.Tensor, npoints: int, radius: float, start_idx: int = 0, thin_start_idx: int = 0):

@@ -1038,17 +1038,25 @@ def pack_scene_data(xyz, rgb, quat, opa, scales, xyz_bones, eef):
     return scene, vis
 
 
-def remove_statistical_outliers(xyz: torch.Tensor, nb_neighbors: int = 50, std_ratio0: float = 2.0, step: float = 0.5):
+def remove_statistical_outliers(xyz: torch.Tensor, nb_neighbors: int = 50, std_ratio0: float = 2.0, step: float = 0.5, knn: str = "dense"):
     """The outlier loop of ``collect_scene_data`` (dynamics_module.py:195-207): repeat Open3D's statistical outlier removal with a
     growing ``std_ratio`` until a pass removes nothing; returns the surviving indices.  Open3D is an absent third-party library:
     its filter is restated from its documentation (mean distance to the ``nb_neighbors`` nearest points, the query included; a
-    point stays if that mean is below cloud mean + std_ratio x sample standard deviation) and is NOT pinned by a golden."""
+    point stays if that mean is below cloud mean + std_ratio x sample standard deviation) and is NOT pinned by a golden.
+    ``knn="dense"`` (the default) takes the distances from a chunked torch.cdist table, ``knn="grid"`` from the exact search of
+    gsdyn.knn_points (O(N) memory): the mean of sqrt(d2) over the k nearest, the query included, either way."""
+    if knn not in ("dense", "grid"):
+        raise ValueError(f"remove_statistical_outliers: knn must be 'dense' or 'grid', got {knn!r}")
     keep = torch.arange(xyz.shape[0], device=xyz.device)
     it = 0
     while True:
         pts = xyz[keep]
         k = min(nb_neighbors, pts.shape[0])
-        md = torch.cat([torch.topk(torch.cdist(pts[s:s + 4096], pts), k, dim=1, largest=False)[0].mean(1) for s in range(0, pts.shape[0], 4096)])
+        if knn == "grid":
+            from .knn import knn_points
+            md = torch.sqrt(knn_points(pts.contiguous(), k)[1]).mean(1)
+        else:
+            md = torch.cat([torch.topk(torch.cdist(pts[s:s + 4096], pts), k, dim=1, largest=False)[0].mean(1) for s in range(0, pts.shape[0], 4096)])
         ok = md < md.mean() + (std_ratio0 + step * it) * md.std()
         if bool(ok.all()):
             return keep

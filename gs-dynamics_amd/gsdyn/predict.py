@@ -135,7 +135,7 @@ def gather_frames(local: dict, dst: int = 0, group=None) -> Optional[dict]:
 def collect_scene_data(model, params: dict, eef_xyz, *, max_nobj: int, fps_radius: float, adj_thresh: float, topk: int, connect_all: bool,
                        dist_thresh: float, n_fps_all: int = 1000, max_steps: int = 1000, low_opacity: float = 0.1,
                        remove_outliers: bool = True, thin_start_idx: int = 0, spatial_sort: bool = True, on_frame=None,
-                       on_skin=None, skin_source=None, tracked_only: bool = False, graph_step: bool = True):
+                       on_skin=None, skin_source=None, tracked_only: bool = False, graph_step: bool = True, outlier_knn: str = "dense"):
     """``DynamicsModule.collect_scene_data`` (/root/reference/src/render/dynamics_module.py:174-257) on the device: ``params`` is
     the tracking result (``params.npz``: means3D [T,P,3] or [P,3], rgb_colors, unnorm_rotations, logit_opacities, log_scales);
     frame 0 is activated, Gaussians with opacity < 0.1 are dropped (:187-192), statistical outliers are excluded from the bone
@@ -153,7 +153,8 @@ def collect_scene_data(model, params: dict, eef_xyz, *, max_nobj: int, fps_radiu
     ``tracked_only``: the rank that rolls out for OTHERS and neither renders nor returns the scene moves only its tracked particles
     (the ``n_fps_all`` farthest points of the inliers, picked here exactly as the rollout would pick them): sampling, relations, network,
     rotation fit and the packets never look at anything else, and the skinning is per particle -- same packets, same keypoints, bit
-    for bit; the returned scene data then hold the tracked particles only."""
+    for bit; the returned scene data then hold the tracked particles only.
+    ``outlier_knn``: how the outlier filter finds its neighbours (``dynamics.remove_statistical_outliers(knn=...)``)."""
     import time
     from . import dynamics as D
     first = lambda t: t[0] if t.dim() == 3 else t   # noqa: E731
@@ -168,7 +169,7 @@ def collect_scene_data(model, params: dict, eef_xyz, *, max_nobj: int, fps_radiu
     if skin_source is not None:
         inlier = torch.zeros(0, dtype=torch.long, device=dev)          # (the receiving side samples nothing)
     else:
-        inlier = D.remove_statistical_outliers(xyz_0) if remove_outliers else torch.arange(xyz_0.shape[0], device=dev)
+        inlier = D.remove_statistical_outliers(xyz_0, knn=outlier_knn) if remove_outliers else torch.arange(xyz_0.shape[0], device=dev)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
@@ -250,7 +251,7 @@ def compose_rgba(im: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 def predict_episode(model, params: dict, eef_xyz, poses: Sequence, w: int, h: int, *, rollout_cfg: dict, rank: Optional[int] = None,
                     world: Optional[int] = None, gather_to: Optional[int] = None, bg=(0.0, 0.0, 0.0), rgba: bool = False,
                     scene_out: Optional[list] = None, overlap: bool = False, pipeline: bool = False, producer: int = 0,
-                    producer_renders: bool = False, group=None):
+                    producer_renders: bool = False, group=None, outlier_knn: str = "dense"):
     """One episode of /root/reference/src/predict.py:74-164 on this rank: GNN rollout (every rank, identical), then this rank's
     (frame, camera) pairs -- colour + all-ones mask render per pair, all cameras of a frame in one rasterizer call.
     ``poses``: the cameras as (w2c, K); ``rollout_cfg``: the keyword arguments of ``collect_scene_data`` (max_nobj, fps_radius,
@@ -265,9 +266,12 @@ def predict_episode(model, params: dict, eef_xyz, poses: Sequence, w: int, h: in
     sequential on both -- two host threads that both spin on device synchronisations need the cores for it; hence not the default.
     ``pipeline`` (world > 1): ONE rank (``producer``) rolls out and broadcasts every moving step's skinning packet (``dynamics.pack_skin``:
     22 floats per bone, 8.8 KB at 100 bones); the other ranks only move the Gaussians with the packets (one skinning launch per frame)
-    and render -- see ``_predict_episode_pipelined``.  Same frames as the replicated form; the rollout leaves the render ranks' time."""
+    and render -- see ``_predict_episode_pipelined``.  Same frames as the replicated form; the rollout leaves the render ranks' time.
+    ``outlier_knn``: ``"dense"`` (the default) or ``"grid"``, handed to ``collect_scene_data`` with ``rollout_cfg``."""
     import time
     dev = params["means3D"].device
+    if outlier_knn != "dense":
+        rollout_cfg = dict(rollout_cfg, outlier_knn=outlier_knn)
     if pipeline:
         w_ = world if world is not None else (dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1)
         if w_ > 1:

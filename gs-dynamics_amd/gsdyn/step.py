@@ -388,9 +388,12 @@ def report_psnr(params, data):
     return calc_psnr(im, data["im"]).mean()
 
 
-def make_rigidity_variables(params, num_knn: int = 20, device=None):
+def make_rigidity_variables(params, num_knn: int = 20, device=None, knn: str = "dense"):
     """Neighbour tensors for the t>0 loss terms (/root/reference/src/tracking/train_utils.py:354-374).
-    The reference builds the kNN with Open3D on the CPU; here a dense torch.cdist top-k (fg points only)."""
+    The reference builds the kNN with Open3D on the CPU; here ``knn="dense"`` (the default) is a dense torch.cdist top-k over the fg points
+    and ``knn="grid"`` the exact search of gsdyn.knn_points (O(N) memory, squared distances from direct differences)."""
+    if knn not in ("dense", "grid"):
+        raise ValueError(f"make_rigidity_variables: knn must be 'dense' or 'grid', got {knn!r}")
     with torch.no_grad():
         is_fg = params["seg_colors"][:, 0] > 0.5
         fg = params["means3D"][is_fg]
@@ -398,10 +401,16 @@ def make_rigidity_variables(params, num_knn: int = 20, device=None):
         n = fg.shape[0]
         k = min(num_knn, max(n - 1, 1))
         idx_chunks, d_chunks = [], []
-        for s in range(0, n, 4096):
-            d = torch.cdist(fg[s:s + 4096], fg)
-            dk, ik = torch.topk(d, k + 1, dim=1, largest=False)
-            idx_chunks.append(ik[:, 1:]); d_chunks.append(dk[:, 1:] ** 2)
+        if knn == "grid":
+            if n > 0:
+                from .knn import knn_points
+                ik, dk = knn_points(fg.contiguous(), k, exclude_self=True)
+                idx_chunks.append(ik); d_chunks.append(dk)
+        else:
+            for s in range(0, n, 4096):
+                d = torch.cdist(fg[s:s + 4096], fg)
+                dk, ik = torch.topk(d, k + 1, dim=1, largest=False)
+                idx_chunks.append(ik[:, 1:]); d_chunks.append(dk[:, 1:] ** 2)
         nbr = torch.cat(idx_chunks) if idx_chunks else torch.zeros((0, k), dtype=torch.long, device=fg.device)
         sq = torch.cat(d_chunks) if d_chunks else torch.zeros((0, k), device=fg.device)
         inv = rot[is_fg].clone()

@@ -59,10 +59,11 @@ def initialize_per_timestep(params, variables, optimizer):
     return params, variables
 
 
-def initialize_post_first_timestep(params, variables, optimizer, num_knn: int = 20):
+def initialize_post_first_timestep(params, variables, optimizer, num_knn: int = 20, knn: str = "dense"):
     """Neighbour tensors + frozen learning rates after t = 0 (/root/reference/src/tracking/train_utils.py:354-374).
-    The reference builds the kNN with Open3D on the host; here a dense torch top-k over the foreground points."""
-    variables.update(make_rigidity_variables(params, num_knn=num_knn))
+    The reference builds the kNN with Open3D on the host; here a dense torch top-k over the foreground points (``knn="dense"``) or the
+    exact device search of gsdyn.knn_points (``knn="grid"``), see ``make_rigidity_variables``."""
+    variables.update(make_rigidity_variables(params, num_knn=num_knn, knn=knn))
     with torch.no_grad():
         variables["prev_pts"] = params["means3D"].detach().clone()
         variables["prev_rot"] = torch.nn.functional.normalize(params["unnorm_rotations"]).detach().clone()
@@ -109,9 +110,10 @@ def train_timestep(params, variables, optimizer, dataset: Sequence[dict], iters:
 
 def train(params, optimizer, timesteps: Sequence[Sequence[dict]], iters_first: int = 10000, iters_next: int = 2000,
           weights: LossWeights = LossWeights(), num_knn: int = 20, views_per_step: int = 1, out_path: Optional[str] = None,
-          seed: Optional[int] = 0, density_control: Optional[dict] = None, scene_radius: Optional[float] = None):
+          seed: Optional[int] = 0, density_control: Optional[dict] = None, scene_radius: Optional[float] = None, knn: str = "dense"):
     """The whole loop over timesteps (``timesteps[t]`` = that timestep's views).  Returns (params, variables, outputs).
-    ``density_control`` + ``scene_radius`` switch on the adaptive density control of the first timestep."""
+    ``density_control`` + ``scene_radius`` switch on the adaptive density control of the first timestep.
+    ``knn``: how the neighbour lists after the first timestep are found (``make_rigidity_variables``)."""
     P = params["means3D"].shape[0]
     variables = init_variables(P, params["means3D"].device)
     if scene_radius is not None:
@@ -126,7 +128,7 @@ def train(params, optimizer, timesteps: Sequence[Sequence[dict]], iters_first: i
                        density_control=density_control if first else None)
         outputs.append(params2cpu(params, first))
         if first:
-            variables = initialize_post_first_timestep(params, variables, optimizer, num_knn)
+            variables = initialize_post_first_timestep(params, variables, optimizer, num_knn, knn=knn)
     if out_path:
         save_params(outputs, out_path)
     return params, variables, outputs

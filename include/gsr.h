@@ -578,6 +578,18 @@ int gsr_plan_cost(int32_t B, int32_t T, int32_t n_obj, int32_t M, const float* s
                   float* collision, float* box_pen, void* stream);
 int gsr_plan_mppi_update(int32_t B, int32_t T, const float* act_seqs, const float* rewards, float reward_weight, float push_length, const float* lower,
                          const float* upper, float* act_seq, int64_t* best_index, float* best_reward, void* stream);
+/* ---- exact k-nearest-neighbour search (csrc/gsr_knn.hip; gsdyn.knn_points).  Additive to ABI 125.
+ * points [N, 3] fp32 on the device -> out_idx [N, k] int64, out_d2 [N, k] fp32.  The distance of query i to point j is
+ *   d2 = (dx*dx + dy*dy) + dz*dz,  dx = p[i].x - p[j].x (and so on), every operation fp32, in that order, unfused;
+ * row i holds the k smallest under the TOTAL order (d2 ascending, then j ascending), in that order.  With exclude_self != 0 the point
+ * j = i is left out by identity (a duplicate of point i is a legitimate neighbour).  The order is total, so the result does not depend on
+ * launch shape or scheduling: bit-identical from call to call.  Rows that involve non-finite coordinates are unspecified (their indices
+ * stay inside [0, N)); no index out of bounds is formed for any input.  No host read-back, everything runs on `stream`.
+ * scratch: gsr_knn_scratch_bytes bytes on the device, 256-byte aligned (O(N): a hash table of cells sized by N, never a dense array
+ * over the bounding box); its contents need not be initialised and are not kept between calls.
+ * 1 <= N <= 2^28, 1 <= k <= 64, k <= N - (exclude_self ? 1 : 0), no NULL pointer: -2 and no launch otherwise. */
+size_t gsr_knn_scratch_bytes(int32_t N); /* host-only */
+int gsr_knn(int32_t N, const float* points, int32_t k, int32_t exclude_self, void* scratch, int64_t* out_idx, float* out_d2, void* stream);
 int gsr_fps(int32_t N, const float* pos, int32_t npoints, int32_t start_idx, float* scratch, int64_t* out_idx, void* stream);
 int gsr_lbs(int32_t P, int32_t n_bones, const float* bones, const float* rotations, const float* translations,
             const float* bone_quats, const float* xyz, const float* quat, float* out_xyz, float* out_quat, void* stream);
