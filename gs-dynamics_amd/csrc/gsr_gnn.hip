@@ -13,6 +13,8 @@
 //   agg[i] = sum over the relations e of receiver i, in list order, of relu(rew1[e] + a2[i] + a3[sender_e])
 // -- (b) replaces, per propagation step, two row gathers, a concatenation, an E x 3H x H product, a zero fill and an index_add.
 namespace gsr_gnn {
+// torch.relu: a NaN stays a NaN (fmaxf(NaN, 0) is 0 -- a diverged particle would silently become "no effect on its neighbours")
+__device__ __forceinline__ float relu(float x) { return x < 0.f ? 0.f : x; }
 __global__ __launch_bounds__(256) void aggregate_kernel(int N, int n_sum, int H, const float* __restrict__ rew1, const float* __restrict__ a23,
                                                         const long long* __restrict__ send, const long long* __restrict__ row_start,
                                                         float* __restrict__ agg, const float* __restrict__ res_a, const float* __restrict__ res_b,
@@ -30,8 +32,8 @@ __global__ __launch_bounds__(256) void aggregate_kernel(int N, int n_sum, int H,
   for (int e = i < n_sum ? (int)row_start[i] : 0; e < e1; ++e) {
     const float4 r1 = *reinterpret_cast<const float4*>(rew1 + (size_t)e * H + k4);
     const float4 a3 = *reinterpret_cast<const float4*>(a23 + (size_t)send[e] * 2 * H + H + k4);
-    sum.x += fmaxf((r1.x + a2.x) + a3.x, 0.f); sum.y += fmaxf((r1.y + a2.y) + a3.y, 0.f);
-    sum.z += fmaxf((r1.z + a2.z) + a3.z, 0.f); sum.w += fmaxf((r1.w + a2.w) + a3.w, 0.f);
+    sum.x += relu((r1.x + a2.x) + a3.x); sum.y += relu((r1.y + a2.y) + a3.y);
+    sum.z += relu((r1.z + a2.z) + a3.z); sum.w += relu((r1.w + a2.w) + a3.w);
   }
   *reinterpret_cast<float4*>(agg + (size_t)i * H + k4) = sum;
 }

@@ -1325,39 +1325,72 @@ def fps_thin(pos: torch.Tensor, npoints: int, radius: float, start_idx: int = 0,
     return out, thin[:m]
 
 
+def _gnn_f32(name, **tensors):
+    for k, t in tensors.items():
+        if not (t.dim() == 2 and t.is_contiguous() and t.dtype == torch.float32):
+            raise ValueError(f"{name}: {k} must be a contiguous float32 matrix")
+
+
+def _gnn_index(name, dev, n, **tensors):
+    for k, t in tensors.items():
+        if not (t.dim() == 1 and t.is_contiguous() and t.dtype == torch.int64 and t.device == dev and int(t.shape[0]) == n):
+            raise ValueError(f"{name}: {k} must be a contiguous int64 vector of {n} entries on the device")
+
+
 def gnn_rel_inputs(rel_nodes: torch.Tensor, receivers: torch.Tensor, senders: torch.Tensor, attr_dim: int, group_dim: int) -> torch.Tensor:
-    """gsr_gnn_rel_inputs: rel_nodes [N, attr + group + state] -> the relation encoder's input rows [E, 2 attr + 1 + state] in one launch."""
+    """gsr_gnn_rel_inputs: rel_nodes [N, attr + group + state] -> the relation encoder's input rows [E, 2 attr + 1 + state] in one launch.
+    rel_nodes contiguous float32, receivers / senders contiguous int64 [E] on its device (ValueError otherwise); E = 0: an empty result,
+    no library call."""
     lib = load_library()
     _require_device(rel_nodes)
     dev = rel_nodes.device
-    E, S = int(receivers.shape[0]), int(rel_nodes.shape[1]) - attr_dim - group_dim
+    _gnn_f32("gnn_rel_inputs", rel_nodes=rel_nodes)
+    attr_dim, group_dim = int(attr_dim), int(group_dim)
+    E, S = int(receivers.shape[0]) if receivers.dim() else -1, int(rel_nodes.shape[1]) - attr_dim - group_dim
+    if attr_dim < 0 or group_dim < 0 or S < 0:
+        raise ValueError("gnn_rel_inputs: rel_nodes must be [N, attr_dim + group_dim + state columns]")
+    _gnn_index("gnn_rel_inputs", dev, E, receivers=receivers, senders=senders)
     with _on(dev):
         out = torch.empty((E, 2 * attr_dim + 1 + S), dtype=torch.float32, device=dev)
         if E:
-            _check(lib.gsr_gnn_rel_inputs(E, int(attr_dim), int(group_dim), S, _ptr(rel_nodes), _ptr(receivers), _ptr(senders), _ptr(out), _stream(dev)),
+            _check(lib.gsr_gnn_rel_inputs(E, attr_dim, group_dim, S, _ptr(rel_nodes), _ptr(receivers), _ptr(senders), _ptr(out), _stream(dev)),
                    "gsr_gnn_rel_inputs")
     return out
 
 
 def gnn_aggregate(rel_part: torch.Tensor, node_parts: torch.Tensor, senders: torch.Tensor, row_start: torch.Tensor, n_sum_rows: int = None, res=None):
-    """gsr_gnn_aggregate: rel_part [E, H], node_parts [N, 2 H], senders [E], row_start [N + 1] (int64; receivers ascending) -> agg [N, H];
-    rows >= n_sum_rows (default N) get zeros.  res = (a, b), two contiguous float32 [N, H]: also returns a + b, written by the same launch
-    (gsr_gnn_aggregate_res) -> (agg, a + b)."""
+    """gsr_gnn_aggregate: rel_part [E, H], node_parts [N, 2 H], senders [E], row_start [N + 1] (int64; receivers ascending) -> agg [N, H]:
+    agg[i] = the sum in list order of relu(rel_part[e] + node_parts[i, :H] + node_parts[senders[e], H:]) over row i's segment, relu as
+    torch.relu (a NaN stays); rows >= n_sum_rows (default N) get zeros.  res = (a, b), two contiguous float32 [N, H]: also returns a + b,
+    written by the same launch (gsr_gnn_aggregate_res) -> (agg, a + b).  The float matrices contiguous float32, the index vectors
+    contiguous int64 on the device, H a multiple of 4 (ValueError otherwise); E = 0: zeros (and a + b), no library call."""
     lib = load_library()
     _require_device(rel_part)
     dev = rel_part.device
-    N, H = int(node_parts.shape[0]), int(rel_part.shape[1])
+    _gnn_f32("gnn_aggregate", rel_part=rel_part, node_parts=node_parts)
+    N, E, H = int(node_parts.shape[0]), int(rel_part.shape[0]), int(rel_part.shape[1])
+    if H <= 0 or H % 4 != 0 or int(node_parts.shape[1]) != 2 * H or node_parts.device != dev:
+        raise ValueError("gnn_aggregate: rel_part [E, H] and node_parts [N, 2 H] on one device with H a multiple of 4, please")
+    _gnn_index("gnn_aggregate", dev, E, senders=senders)
+    _gnn_index("gnn_aggregate", dev, N + 1, row_start=row_start)
+    n_sum = N if n_sum_rows is None else int(n_sum_rows)
+    if not 0 <= n_sum <= N:
+        raise ValueError("gnn_aggregate: n_sum_rows must lie in [0, N]")
     with _on(dev):
-        agg = torch.empty((N, H), dtype=torch.float32, device=dev)
         if res is not None:
             ra, rb = res
-            if not all(t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (N, H) for t in (ra, rb)):
+            if not all(t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (N, H) and t.device == dev for t in (ra, rb)):
                 raise ValueError("gnn_aggregate(res=...): two contiguous float32 [N, H] tensors, please")
+        if E == 0 or N == 0:          # no relation: nothing to sum (an empty tensor has no address for the library to take)
+            agg = torch.zeros((N, H), dtype=torch.float32, device=dev)
+            return agg if res is None else (agg, ra + rb)
+        agg = torch.empty((N, H), dtype=torch.float32, device=dev)
+        if res is not None:
             out = torch.empty((N, H), dtype=torch.float32, device=dev)
-            _check(lib.gsr_gnn_aggregate_res(N, N if n_sum_rows is None else int(n_sum_rows), H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(row_start),
+            _check(lib.gsr_gnn_aggregate_res(N, n_sum, H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(row_start),
                                              _ptr(agg), _ptr(ra), _ptr(rb), _ptr(out), _stream(dev)), "gsr_gnn_aggregate_res")
             return agg, out
-        _check(lib.gsr_gnn_aggregate(N, N if n_sum_rows is None else int(n_sum_rows), H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(row_start), _ptr(agg), _stream(dev)), "gsr_gnn_aggregate")
+        _check(lib.gsr_gnn_aggregate(N, n_sum, H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(row_start), _ptr(agg), _stream(dev)), "gsr_gnn_aggregate")
     return agg
 
 

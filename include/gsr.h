@@ -517,6 +517,8 @@ int gsr_fit_bones(int32_t n_bones, const float* bones, const float* motions, con
  *   relu(rel_part[e] + node_parts[i][0 : width] + node_parts[senders[e]][width : 2 width]),  rel_part [n_rel, width] = relation_encode
  *   @ W1^T + b, node_parts [n_rows, 2 width] = effect @ [W2 | W3]^T with W = [W1 | W2 | W3] the relation propagator's weight: what
  *   relation_propagator(cat(relation_encode, effect[recv], effect[send])) followed by the index_add onto the receivers computes.
+ *   relu as torch.relu: a NaN stays a NaN (x < 0 ? 0 : x, not fmaxf); each term is (rel_part + node_parts[i]) + node_parts[sender], added
+ *   to a running fp32 sum that starts at zero.  n_rel = 0 is the caller's to serve (NULL pointers are refused with -2).
  *   Rows >= n_sum_rows get zeros (a padded graph's dummy last row collects every dummy relation: hundreds, walked by one thread each). */
 int gsr_gnn_rel_inputs(int32_t n_rel, int32_t attr_dim, int32_t group_dim, int32_t state_cols, const float* rel_nodes, const int64_t* receivers,
                        const int64_t* senders, float* out, void* stream);
