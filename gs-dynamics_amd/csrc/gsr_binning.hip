@@ -15,7 +15,9 @@
 //                       wave come from wave-64 __ballot peer masks, histograms live in LDS, and no global
 //                       atomics are used anywhere, so the result is deterministic;
 //   3. tile ranges      found by the LAST scatter pass itself (atomicMin / atomicMax of the run ends per block);
-//   4. tile_sort        one workgroup per tile sorts its segment by depth: a stable LSD radix sort on the 32
+//   4. tile_sort        short segments (<= 512 entries) by one wave in registers, segments of 513 .. 1016 entries by a pair of
+//                       waves (compare-exchange network on the unique 64-bit key); a longer one by a workgroup: a stable
+//                       LSD radix sort on the 32
 //                       depth bits inside LDS (segments arrive in Gaussian-id order, so stability gives the
 //                       reference tie rule); segments of 2049..4096 entries use a compare-exchange network
 //                       on the unique 64-bit key (depth_bits << 32 | gaussian_id) in LDS, larger ones the
@@ -481,7 +483,8 @@ __global__ __launch_bounds__(GSR_BLOCK) void radix_scatter_kernel(GsrBinViews ta
 // tile_sort's wave path (one wave per tile, entries in registers, no barriers) takes lists up to tab.wave_cap entries; longer ones
 // get a workgroup each.  512 for ordinary scenes -- a lone wave sorting 800 entries is slower than a workgroup, and with only a few
 // such tiles it is the launch's tail (800^2 / 100 k, one view: tile_sort 17 -> 31 us with 1024) -- and 1024 when the lists are long
-// on average (1080p / 500 k: 735 entries per tile, tile_sort 589 -> 547 us per frame).
+// on average (1080p / 500 k: 735 entries per tile, tile_sort 589 -> 547 us per frame).  (Ordinary scenes: the workgroup that takes the
+// lists of 513 .. 1016 entries sorts TWO of them, a pair of waves each -- tile_sort_pair_tickets -- and not one with its LDS radix sort.)
 // n > 512 <=> (n + 7) >> 3 >= 65 <=> bucket <= 190: the long tickets end where bucket 191 starts (the fourth bucket of lane 47);
 // n > 1024 <=> bucket <= 126: lane 31.
 #define ORD_WAVES 16
@@ -1112,9 +1115,15 @@ __device__ __forceinline__ void wave_sort_step(uint64_t (&x)[NR], int lane) {
   }
 }
 template <int LK, int NR>
+__device__ __forceinline__ void wave_sort_halfcleaners(uint64_t (&x)[NR], int lane);
+template <int LK, int NR>
 __device__ __forceinline__ void wave_sort_stage(uint64_t (&x)[NR], int lane) {   // merge size k = 2^LK
+  wave_sort_step<(1 << LK) - 1, NR>(x, lane);      // the mirror step
+  wave_sort_halfcleaners<LK, NR>(x, lane);
+}
+template <int LK, int NR>
+__device__ __forceinline__ void wave_sort_halfcleaners(uint64_t (&x)[NR], int lane) {   // the steps of merge size 2^LK behind its mirror step: strides 2^(LK - 2) .. 1
   static_assert(LK <= 11, "the half-cleaner steps below stop at stride 512");
-  wave_sort_step<(1 << LK) - 1, NR>(x, lane);
   if constexpr (LK >= 11) wave_sort_step<512, NR>(x, lane);
   if constexpr (LK >= 10) wave_sort_step<256, NR>(x, lane);
   if constexpr (LK >= 9) wave_sort_step<128, NR>(x, lane);
@@ -1127,6 +1136,8 @@ __device__ __forceinline__ void wave_sort_stage(uint64_t (&x)[NR], int lane) {  
   if constexpr (LK >= 2) wave_sort_step<1, NR>(x, lane);
 }
 template <int NR>
+__device__ __forceinline__ void wave_sort_store(const uint64_t (&x)[NR], uint32_t* __restrict__ out, uint32_t e0, uint32_t n);
+template <int NR>
 __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ seg, uint32_t* __restrict__ out, uint32_t n, int lane) {
   uint64_t x[NR];
 #pragma unroll
@@ -1138,8 +1149,11 @@ __device__ __forceinline__ void wave_sort_tile(const uint64_t* __restrict__ seg,
   if constexpr (NR >= 8) wave_sort_stage<9, NR>(x, lane);
   if constexpr (NR >= 16) wave_sort_stage<10, NR>(x, lane);
   if constexpr (NR >= 32) wave_sort_stage<11, NR>(x, lane);
-  // rank e = lane * NR + r sits in register r of lane `lane`: a lane stores its NR consecutive ids (16 bytes at a time where aligned)
-  const uint32_t e0 = (uint32_t)lane * NR;
+  wave_sort_store<NR>(x, out, (uint32_t)lane * NR, n);
+}
+// rank e0 + r sits in register r of this lane: a lane stores its NR consecutive ids (16 bytes at a time where aligned)
+template <int NR>
+__device__ __forceinline__ void wave_sort_store(const uint64_t (&x)[NR], uint32_t* __restrict__ out, uint32_t e0, uint32_t n) {
   if constexpr (NR >= 4) {
     if ((((uintptr_t)out) & 15u) == 0 && e0 + NR <= n) {
 #pragma unroll
@@ -1233,6 +1247,110 @@ __device__ __forceinline__ int tile_radix_sort(TileSortLds<RCAP, NW>& L, uint32_
   return cur;
 }
 
+// ---- lists of 513 .. 1016 entries in an ordinary scene: TWO WAVES per list, the keys in registers.
+// 40 % of the busy tiles of the benchmark's views are in this class, and the LDS radix sort by a 4-wave workgroup spent 18.6 us on each at
+// four views (12.5 us alone on the chip) against the 11 us ONE wave needs for 512 keys: 133 000 of the launch's 155 000 wave-us
+// (profiles/tile_sort_ticket_classes.txt).  Here the lower wave of a pair sorts the entries [0, 512) with the steps of wave_sort_tile<8>
+// (merge sizes 2 .. 512) and the upper wave the m = n - 512 others with those of wave_sort_tile<NRU>, NRU = 1, 2, 4 or 8 keys per lane
+// for m <= KU = 64, 128, 256, 512 (the mean list of the class has 650 entries: the upper wave of most pairs has a fraction of the lower
+// one's work).  The mirror step of the 1024-merge pairs rank a of the lower half with rank 511 - a of the upper one -- through LDS, 4 KiB
+// per wave, one workgroup barrier; ranks KU and above of the upper half are padding, which no step of the network moves, so the lower wave
+// keeps its key there -- and the half-cleaner steps behind it stay inside each wave: strides 256 .. 1 below, KU / 2 .. 1 above (the
+// wider ones would meet padding only).  Same network, same unique 64-bit key and ~0 padding as every other path, so the list is the same
+// bits.  A workgroup takes two such tickets (waves 0, 1 and waves 2, 3); the exchange lives in the workgroup paths' LDS block (`net`), so
+// the kernel's LDS, and with it the occupancy of the shorter lists, is what it was.
+// (Wave priority by length class -- s_setprio 2 for the pair waves, 1 for the 257 .. 512 class -- was measured by itself and on top of the
+// pairs: 30.6 us against the parent's 30.9, 21.8 against 22.3, inside the 0.6 us between rounds.  The launch is bound by the SUM of the
+// tickets' work, which a priority only reorders: not kept.  profiles/tile_sort_critical_path.txt)
+template <int RCAP, int NW>
+__device__ __forceinline__ TileSortLds<RCAP, NW>& tile_sort_lds() {
+  __shared__ TileSortLds<RCAP, NW> L;
+  return L;
+}
+// LDS slot of sorted rank `pos` of a wave that holds NR keys per lane (rank = lane * NR + register): register-major, so that the owner's
+// stores are conflict-free
+__device__ __forceinline__ uint32_t pair_slot(uint32_t pos, uint32_t lnr) { return ((pos & ((1u << lnr) - 1u)) << 6) + (pos >> lnr); }
+// The upper wave of a pair, before the exchange: its m <= 64 NR keys sorted and published; x[0 .. NR) keeps them across the barrier.
+template <int NR>
+__device__ __forceinline__ void pair_upper_sort(uint64_t (&x)[8], uint64_t* __restrict__ mine, const uint64_t* __restrict__ seg, uint32_t n, int lane) {
+  constexpr int LNR = gsr_log2<NR>::value;
+  uint64_t y[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) { const uint32_t e = 512u + (uint32_t)(r * 64 + lane); y[r] = e < n ? seg[e] : ~0ull; }
+  wave_sort_stage<1, NR>(y, lane); wave_sort_stage<2, NR>(y, lane); wave_sort_stage<3, NR>(y, lane);
+  wave_sort_stage<4, NR>(y, lane); wave_sort_stage<5, NR>(y, lane); wave_sort_stage<6, NR>(y, lane);
+  if constexpr (NR >= 2) wave_sort_stage<7, NR>(y, lane);
+  if constexpr (NR >= 4) wave_sort_stage<8, NR>(y, lane);
+  if constexpr (NR >= 8) wave_sort_stage<9, NR>(y, lane);
+#pragma unroll
+  for (int r = 0; r < NR; ++r) { mine[pair_slot((uint32_t)(lane * NR + r), LNR)] = y[r]; x[r] = y[r]; }
+}
+// ... and behind it: rank j of the upper half keeps the maximum of itself and rank 511 - j of the lower half, then the half-cleaners
+template <int NR>
+__device__ __forceinline__ void pair_upper_merge(uint64_t (&x)[8], const uint64_t* __restrict__ lower, uint32_t* __restrict__ out, uint32_t n, int lane) {
+  uint64_t y[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const uint64_t o = lower[pair_slot(511u - (uint32_t)(lane * NR + r), 3)];
+    y[r] = o > x[r] ? o : x[r];
+  }
+  wave_sort_halfcleaners<gsr_log2<NR>::value + 7, NR>(y, lane);       // strides 32 NR .. 1
+  wave_sort_store<NR>(y, out, 512u + (uint32_t)lane * NR, n);
+}
+template <int RCAP, int NW>
+__device__ __forceinline__ void tile_sort_pair_tickets(const GsrBinViews& tab, int cur, uint32_t ticket0, uint32_t n_long) {
+  static_assert(NW == 4 && 2 * RCAP >= 4 * 512, "two pairs of waves, 512 keys per wave in the network block");
+  TileSortLds<RCAP, NW>& L = tile_sort_lds<RCAP, NW>();
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const bool upper = (wv & 1) != 0;
+  const uint32_t ticket = ticket0 + (uint32_t)(wv >> 1);
+  bool live = ticket < n_long;                  // (an odd number of such lists: the last workgroup's second pair has none)
+  uint32_t n = 0;
+  const uint64_t* seg = nullptr;
+  uint32_t* out = nullptr;
+  if (live) {
+    const uint4 ord = tab.order[ticket];
+    const GsrBinView& vw = tab.v[__builtin_amdgcn_readfirstlane(ord.w)];
+    live = !vw.shares_lists;                    // sorted as part of the view that owns the lists
+    n = __builtin_amdgcn_readfirstlane(ord.z - ord.y);
+    seg = vw.dg[cur] + ord.y;
+    out = vw.point_list + ord.y;
+  }
+  const uint32_t m = n > 512u ? n - 512u : 0u;  // keys of the upper wave (1 .. 504), 64 << lnru of them with the padding
+  const uint32_t lnru = m <= 64u ? 0u : m <= 128u ? 1u : m <= 256u ? 2u : 3u;
+  uint64_t x[8];
+  uint64_t* mine = L.net + wv * 512;
+  if (live && !upper) {                         // (the branches are uniform per wave; the barrier below is reached by all four waves)
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { const uint32_t e = (uint32_t)(r * 64 + lane); x[r] = e < n ? seg[e] : ~0ull; }
+    wave_sort_stage<1, 8>(x, lane); wave_sort_stage<2, 8>(x, lane); wave_sort_stage<3, 8>(x, lane);
+    wave_sort_stage<4, 8>(x, lane); wave_sort_stage<5, 8>(x, lane); wave_sort_stage<6, 8>(x, lane);
+    wave_sort_stage<7, 8>(x, lane); wave_sort_stage<8, 8>(x, lane); wave_sort_stage<9, 8>(x, lane);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) mine[pair_slot((uint32_t)(lane * 8 + r), 3)] = x[r];
+  } else if (live) {
+    if (lnru == 0u) pair_upper_sort<1>(x, mine, seg, n, lane);
+    else if (lnru == 1u) pair_upper_sort<2>(x, mine, seg, n, lane);
+    else if (lnru == 2u) pair_upper_sort<4>(x, mine, seg, n, lane);
+    else pair_upper_sort<8>(x, mine, seg, n, lane);
+  }
+  __syncthreads();
+  if (!live) return;
+  const uint64_t* theirs = L.net + (wv ^ 1) * 512;
+  if (!upper) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {               // rank a keeps the minimum of itself and rank 511 - a of the upper half, where that is a key
+      const uint32_t j = 511u - (uint32_t)(lane * 8 + r);
+      if (j < (64u << lnru)) { const uint64_t o = theirs[pair_slot(j, lnru)]; x[r] = o < x[r] ? o : x[r]; }
+    }
+    wave_sort_halfcleaners<10, 8>(x, lane);     // strides 256 .. 1
+    wave_sort_store<8>(x, out, (uint32_t)lane * 8u, n);
+  } else if (lnru == 0u) pair_upper_merge<1>(x, theirs, out, n, lane);
+  else if (lnru == 1u) pair_upper_merge<2>(x, theirs, out, n, lane);
+  else if (lnru == 2u) pair_upper_merge<4>(x, theirs, out, n, lane);
+  else pair_upper_merge<8>(x, theirs, out, n, lane);
+}
+
 // MODE 0: both kinds of ticket in one launch (blocks below n_long: a workgroup per long list, the others: a wave per short list).
 // The workgroup paths' LDS block then bounds the occupancy of the wave-sorted lists too: 2 workgroups per CU with the 68 KiB of the
 // RCAP = 4096 build.  So that build launches twice: MODE 2 = the wave tickets alone in a kernel WITHOUT any LDS (6 waves per SIMD, the
@@ -1251,9 +1369,26 @@ __device__ __forceinline__ void tile_sort_long_ticket(const GsrBinViews& tab, in
 // MODE 3 (dense scenes, wave_cap = 2048): the lists of 1025 .. 2032 entries -- 83 % of the entries of a configs[4] frame -- each by ONE wave
 // with 32 keys per lane in registers (tickets [n_long, queue[3])), a launch of its own (its register count would cost the shorter lists
 // their occupancy); MODE 2 then starts at queue[3].
+#ifdef GSR_TRACE_SORT
+// Debug build (tools/sort_ticket_classes.py; off in the shipped library): per sort ticket {start, end (wall_clock64, 100 MHz), workgroup | kind << 24,
+// list length} -- kind 0: a wave's ticket, 1: a workgroup's (LDS paths), 2: a pair of waves', 3: a 32-keys-per-lane wave -- and per workgroup of the one-launch
+// builds the moment it entered the kernel.  The arrays hold the LAST call's launches (the same ticket ids overwrite).
+#define GSR_SORT_TRACE_MAX 65536
+__device__ uint4 g_sort_trace[GSR_SORT_TRACE_MAX];
+__device__ uint32_t g_sort_wg_start[GSR_SORT_TRACE_MAX];
+#define GSR_SORT_TRACE(ticket, kind, n)                                                                     \
+  do { if ((threadIdx.x & ((kind) == 2 ? 127 : 63)) == 0 && ((kind) != 1 || threadIdx.x == 0) && (ticket) < GSR_SORT_TRACE_MAX) \
+         g_sort_trace[ticket] = make_uint4((uint32_t)tr0, (uint32_t)wall_clock64(), blockIdx.x | ((uint32_t)(kind) << 24), n); } while (0)
+#else
+#define GSR_SORT_TRACE(ticket, kind, n) do { } while (0)
+#endif
 template <int RCAP, int MODE = 0, int NW = 4>
 __global__ __launch_bounds__(64 * NW, (RCAP <= 1024 || MODE == 2) ? TS_MIN_WAVES : (MODE == 3 ? TS_W32_WAVES : 1)) void tile_sort_kernel(GsrBinViews tab, int cur) {
   const int tid = threadIdx.x;
+#ifdef GSR_TRACE_SORT
+  unsigned long long tr0 = wall_clock64();
+  if (MODE == 0 && tid == 0 && blockIdx.x < GSR_SORT_TRACE_MAX) g_sort_wg_start[blockIdx.x] = (uint32_t)tr0;
+#endif
   if constexpr (MODE == 3) {
     const uint32_t n_long3 = tab.queue[6], n_mid = tab.queue[3];
     const uint32_t ticket = n_long3 + blockIdx.x * 4u + (uint32_t)(tid >> 6);
@@ -1263,14 +1398,34 @@ __global__ __launch_bounds__(64 * NW, (RCAP <= 1024 || MODE == 2) ? TS_MIN_WAVES
     if (vw.shares_lists) return;
     const uint32_t n = __builtin_amdgcn_readfirstlane(ord.z - ord.y);
     wave_sort_tile<32>(vw.dg[cur] + ord.y, vw.point_list + ord.y, n, tid & 63);
+    GSR_SORT_TRACE(ticket, 3, n);
     return;
   }
   // The order array leads with the longest lists.  Its first n_long tickets (n > TS_WAVE_CAP) take a whole workgroup
   // each; behind them every WAVE takes one ticket (register-resident wave sort, no barriers).
   const uint32_t n_busy = tab.queue[4], n_long = tab.queue[6];
-  if (MODE == 2 || (MODE == 0 && blockIdx.x >= n_long)) {
+  // Ordinary scenes (wave_cap 512: n_long = the lists above 512 entries, queue[2] of them above 1016): the tickets [queue[2], n_long) go
+  // two to a workgroup (tile_sort_pair_tickets), so the workgroups of the wave tickets start that much earlier in the grid.  Both counts are the
+  // tile order's, on the device: nothing here waits for the host, in capacity mode as in any other.
+  uint32_t wave_block0 = n_long;                 // the workgroup that holds the first wave ticket
+  if constexpr (MODE == 0 && RCAP <= 1024) {
+    if (tab.wave_cap == 512) {
+      const uint32_t n_vlong = min(tab.queue[2], n_long);
+      wave_block0 = n_vlong + ((n_long - n_vlong + 1u) >> 1);
+      if (blockIdx.x >= n_vlong && blockIdx.x < wave_block0) {
+        const uint32_t ticket0 = n_vlong + 2u * (blockIdx.x - n_vlong);
+        tile_sort_pair_tickets<RCAP, NW>(tab, cur, ticket0, n_long);
+#ifdef GSR_TRACE_SORT
+        const uint32_t tk = ticket0 + (uint32_t)(tid >> 7);
+        if (tk < n_long) GSR_SORT_TRACE(tk, 2, tab.order[tk].z - tab.order[tk].y);
+#endif
+        return;
+      }
+    }
+  }
+  if (MODE == 2 || (MODE == 0 && blockIdx.x >= wave_block0)) {
     const uint32_t first = (MODE == 2 && tab.wave_cap == 2048) ? tab.queue[3] : n_long;      // (wave_cap 2048: MODE 3 took [n_long, queue[3]))
-    const uint32_t ticket = first + (MODE == 2 ? blockIdx.x : blockIdx.x - n_long) * 4u + (uint32_t)(tid >> 6);
+    const uint32_t ticket = first + (MODE == 2 ? blockIdx.x : blockIdx.x - wave_block0) * 4u + (uint32_t)(tid >> 6);
     if (ticket >= n_busy) return;
     const uint4 ord = tab.order[ticket];
     const GsrBinView& vw = tab.v[__builtin_amdgcn_readfirstlane(ord.w)];
@@ -1283,6 +1438,7 @@ __global__ __launch_bounds__(64 * NW, (RCAP <= 1024 || MODE == 2) ? TS_MIN_WAVES
     else if (n <= 256) wave_sort_tile<4>(seg, out, n, tid & 63);
     else if (n <= 512) wave_sort_tile<8>(seg, out, n, tid & 63);
     else wave_sort_tile<16>(seg, out, n, tid & 63);
+    GSR_SORT_TRACE(ticket, 0, n);
     return;
   }
   if constexpr (MODE == 1) {
@@ -1293,7 +1449,11 @@ __global__ __launch_bounds__(64 * NW, (RCAP <= 1024 || MODE == 2) ? TS_MIN_WAVES
     const uint32_t n_mine = tab.wave_cap == 512 ? tab.queue[2] : n_long;
     for (uint32_t ticket = blockIdx.x; ticket < n_mine; ticket += gridDim.x) {
       tile_sort_long_ticket<RCAP, NW>(tab, cur, ticket);
+      GSR_SORT_TRACE(ticket, 1, tab.order[ticket].z - tab.order[ticket].y);
       __syncthreads();                           // the LDS block is the next ticket's
+#ifdef GSR_TRACE_SORT
+      tr0 = wall_clock64();
+#endif
     }
   } else if constexpr (MODE != 2) {
     if (blockIdx.x >= n_long) return;
@@ -1302,12 +1462,13 @@ __global__ __launch_bounds__(64 * NW, (RCAP <= 1024 || MODE == 2) ? TS_MIN_WAVES
     // 4096-entry block that follows (round 5: the build is chosen per ticket, not per scene) -- when the launcher issued it
     if (RCAP <= 1024 && tab.vlong_launch && blockIdx.x < tab.queue[2]) return;
     tile_sort_long_ticket<RCAP, NW>(tab, cur, blockIdx.x);
+    GSR_SORT_TRACE(blockIdx.x, 1, tab.order[blockIdx.x].z - tab.order[blockIdx.x].y);
   }
 }
 
 template <int RCAP, int NW>
 __device__ __forceinline__ void tile_sort_long_ticket(const GsrBinViews& tab, int cur, uint32_t ticket) {
-  __shared__ TileSortLds<RCAP, NW> L;
+  TileSortLds<RCAP, NW>& L = tile_sort_lds<RCAP, NW>();
   constexpr uint32_t NT = 64 * NW;
   const int tid = threadIdx.x;
   const uint4 ord = tab.order[ticket];         // longest lists are dispatched first
@@ -1416,6 +1577,16 @@ int gsr_launch_shared_lists(const GsrBinViews& tab_in, int P, uint32_t D, const 
   GSR_HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+#ifdef GSR_TRACE_SORT
+extern "C" int gsr_debug_sort_trace(uint32_t* out4, uint32_t* wg_start, int n) {   // debug builds only: not part of include/gsr.h
+  GSR_HIP_CHECK(hipDeviceSynchronize());
+  const size_t m = (size_t)(n < GSR_SORT_TRACE_MAX ? n : GSR_SORT_TRACE_MAX);
+  GSR_HIP_CHECK(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_sort_trace), sizeof(uint4) * m));
+  GSR_HIP_CHECK(hipMemcpyFromSymbol(wg_start, HIP_SYMBOL(g_sort_wg_start), sizeof(uint32_t) * m));
+  return 0;
+}
+#endif
 
 int gsr_launch_scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* total_out, hipStream_t st) {
   { GSR_PROF("scan", st);
@@ -1570,7 +1741,8 @@ int gsr_launch_binning(const GsrBinViews& tab_in, int P, hipStream_t st) {
     } else
       {
         // ordinary scenes: the 1024-entry LDS block (20 KiB: eight workgroups per CU -- the wave-sorted lists are the bulk of the work
-        // and want the occupancy); GSR_TILE_SORT_RCAP=2048 keeps the 36 KiB build
+        // and want the occupancy; the pairs of waves that sort the lists of 513 .. 1016 entries exchange through the same block);
+        // GSR_TILE_SORT_RCAP=2048 keeps the 36 KiB build, whose workgroups sort those lists with the LDS radix sort
         const bool small_lds = !(force && force[0] == '2');
         if (small_lds) {
           hipLaunchKernelGGL(tile_sort_kernel<1024>, dim3(tab.V * tab.T), dim3(GSR_BLOCK), 0, st, tab, cur);
