@@ -487,6 +487,30 @@ __device__ __forceinline__ float gsr_wave_sum_to_lane63(float v) {
   v = gsr_dpp_add<0x143, 0xC>(v);
   return v;
 }
+// Wave minimum of 64-bit keys, the same value in every lane: the six DPP steps of the sum above (both halves moved with the same
+// control; lanes a step does not reach read the identity ~0) leave it in lane 63, two readlanes broadcast it.  A 64-bit __shfl_xor
+// butterfly would be twelve ds_bpermute round trips per minimum.  A wave maximum is ~gsr_wave_min64(~v).
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ unsigned long long gsr_dpp_min64(unsigned long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)v, CTRL, ROW_MASK, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+  return o < v ? o : v;
+}
+__device__ __forceinline__ unsigned long long gsr_wave_min64(unsigned long long v) {
+  v = gsr_dpp_min64<0xB1>(v); v = gsr_dpp_min64<0x4E>(v); v = gsr_dpp_min64<0x141>(v); v = gsr_dpp_min64<0x140>(v);
+  v = gsr_dpp_min64<0x142, 0xA>(v); v = gsr_dpp_min64<0x143, 0xC>(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// Minimum that keeps a NaN (as torch.min does) and is evaluated in a fixed order; a maximum is gsr_min_nan of the negated values.
+__device__ __forceinline__ float gsr_min_nan(float a, float b) { return (b < a || b != b) ? b : a; }
+// ... over the 64 lanes of a wave as an xor butterfly, offsets 32, 16, .. 1; every lane holds the result.
+__device__ __forceinline__ float gsr_wave_min_nan(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = gsr_min_nan(v, __shfl_xor(v, off, 64));
+  return v;
+}
 // Nine wave sums at once (the backward's per-entry gradient partials), totals valid in lane 63.
 // Written as ONE stage-major block of 54 fused v_add_f32_dpp: hipcc otherwise SLP-packs the adds into
 // v_pk_add_f32, which blocks the mov_dpp+add fusion (2.5 instructions per step instead of 1), and cannot

@@ -6,6 +6,7 @@
 //             /root/reference/src/render/utils.py:207-239).
 #include <stdlib.h>
 #include "gsr_common.h"
+#include "gsr_relations.h"
 
 // kernels live in a NAMED namespace: profilers and traces show gsr_dynamics::<kernel>, not "(anonymous namespace)"
 namespace gsr_dynamics {
@@ -244,35 +245,13 @@ __global__ __launch_bounds__(64) void fps_thin_wave_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- relations of a rollout step, fixed shapes
-// construct_edges (gsdyn.dynamics; /root/reference/src/data/dataset.py:88-147) for the rollout's graph -- object particles 0 .. n_obj_cap - 1
+// construct_edges (gsdyn.dynamics; the reference's data/dataset.py:88-147) for the rollout's graph -- object particles 0 .. n_obj_cap - 1
 // of which the first *n_valid are real, ONE tool particle at index n_obj_cap -- as one launch with padded outputs: receiver / sender
 // lists of e_cap entries (row-major order of the adjacency matrix, as torch's nonzero gives them; unused entries = `dummy`) and the
-// count.  A pair is related when both ends are real, not both tools, closer than thr (squared distance (dx*dx + dy*dy) + dz*dz < thr2,
-// rounded as the torch expression) and -- among objects -- the sender is one of the receiver's topk nearest objects (itself included;
-// equal distances: the lower index first).  One workgroup, one receiver per thread.
-// Round 4: one WAVE per receiver (16 waves, receivers w, w + 16, ...), lane l holds the senders l and l + 64 (N <= 128).  The k nearest
-// objects of a receiver are found as k successive wave minima of the 64-bit keys (distance bits << 32 | sender) above the previous one
-// -- ties go to the lower index by construction -- so the k-th key is a threshold and membership one compare; the relations of a row
-// are two ballots.  (Round 3's form -- one THREAD per receiver walking all senders through a 16-deep insertion list, three times --
-// issued ~30 k instructions from two waves: 96 us of the 0.8 ms rollout step; this one 6 us.)
+// count.  Which pairs are related, and how a row becomes masks and list entries: gsr_relations.h.  One workgroup, one WAVE per receiver
+// (16 waves, receivers w, w + 16, ...): 6 us.  (One THREAD per receiver walking all senders through a 16-deep insertion list, three
+// times, issues ~30 k instructions from two waves: 96 us of the 0.8 ms rollout step.)
 #define CE_THREADS 1024
-#define CE_MAXK 16
-// wave minimum of 64-bit keys, the same value in every lane: six DPP steps (both halves moved with the same control; lanes a step does
-// not reach read the identity ~0) leave it in lane 63, two readlanes broadcast it -- the butterfly of 64-bit __shfl_xor it replaces was
-// twelve ds_bpermute round trips per minimum, five minima per receiver.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ unsigned long long ce_dpp_min(unsigned long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)v, CTRL, ROW_MASK, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xf, false);
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-  return o < v ? o : v;
-}
-__device__ __forceinline__ unsigned long long ce_wave_min(unsigned long long v) {
-  v = ce_dpp_min<0xB1>(v); v = ce_dpp_min<0x4E>(v); v = ce_dpp_min<0x141>(v); v = ce_dpp_min<0x140>(v);
-  v = ce_dpp_min<0x142, 0xA>(v); v = ce_dpp_min<0x143, 0xC>(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
 __global__ __launch_bounds__(CE_THREADS) void construct_edges_kernel(const float* __restrict__ pos, int n_obj_cap, const int* __restrict__ n_valid_p,
                                                                    float thr2, int topk, long long dummy, int e_cap,
                                                                    long long* __restrict__ recv, long long* __restrict__ send,
@@ -286,67 +265,20 @@ __global__ __launch_bounds__(CE_THREADS) void construct_edges_kernel(const float
   const int N = n_obj_cap + 1, n_valid = min(*n_valid_p, n_obj_cap);
   if (tid < N) { sp[3 * tid] = pos[3 * tid]; sp[3 * tid + 1] = pos[3 * tid + 1]; sp[3 * tid + 2] = pos[3 * tid + 2]; }
   __syncthreads();
-  const int k = min(min(topk, CE_MAXK), n_valid);
+  const int k = min(min(topk, GSR_REL_MAXK), n_valid);
   for (int i = wv; i < N; i += CE_THREADS / 64) {
-    const bool i_tool = i == n_obj_cap, i_obj = i < n_valid;
-    const float px = sp[3 * i], py = sp[3 * i + 1], pz = sp[3 * i + 2];
-    unsigned long long key[2];
-    bool near_[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = lane + 64 * h;
-      float d = __builtin_inff();
-      if (j < N) {
-        const float dx = px - sp[3 * j], dy = py - sp[3 * j + 1], dz = pz - sp[3 * j + 2];
-        d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      }
-      near_[h] = d < thr2;
-      key[h] = j < n_valid ? (((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j) : ~0ull;   // (d >= 0: its bits order like its value)
-    }
-    // the receiver's k-th nearest object as a key: k minima, each above the one before
-    unsigned long long kth = 0ull;
-    bool first = true;
-    if (i_obj)
-      for (int q = 0; q < k; ++q) {
-        const unsigned long long c0 = (first || key[0] > kth) ? key[0] : ~0ull, c1 = (first || key[1] > kth) ? key[1] : ~0ull;
-        kth = ce_wave_min(c0 < c1 ? c0 : c1);
-        first = false;
-      }
     unsigned long long m[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = lane + 64 * h;
-      const bool j_tool = j == n_obj_cap, j_obj = j < n_valid;
-      bool rel = (i_obj || i_tool) && (j_tool || j_obj) && !(i_tool && j_tool) && near_[h];
-      if (i_obj && j_obj) rel = rel && key[h] <= kth;
-      m[h] = __ballot(rel);
-    }
+    gsr_rel_row_masks(sp, i, lane, N, n_obj_cap, n_valid, thr2, k, m);
     if (lane == 0) { s_mask[i][0] = m[0]; s_mask[i][1] = m[1]; }
   }
   __syncthreads();
-  if (wv == 0) {        // exclusive scan of the row counts (N <= 128: two rows per lane)
-    const int c0 = lane < N ? __popcll(s_mask[lane][0]) + __popcll(s_mask[lane][1]) : 0;
-    const int c1 = lane + 64 < N ? __popcll(s_mask[lane + 64][0]) + __popcll(s_mask[lane + 64][1]) : 0;
-    int inc0 = c0, inc1 = c1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o0 = __shfl_up(inc0, d, 64), o1 = __shfl_up(inc1, d, 64);
-      if (lane >= d) { inc0 += o0; inc1 += o1; }
-    }
-    const int tot0 = __shfl(inc0, 63, 64);
-    s_base[lane] = inc0 - c0;
-    s_base[lane + 64] = tot0 + inc1 - c1;
-    if (lane == 63) s_total = tot0 + inc1;
+  if (wv == 0) {
+    const int t = gsr_rel_scan_rows(s_mask, lane, N, s_base);
+    if (lane == 63) s_total = t;
   }
   __syncthreads();
   const int total = s_total;
-  for (int i = wv; i < N; i += CE_THREADS / 64) {       // row-major order of the adjacency matrix, as torch's nonzero gives it
-    const unsigned long long m0 = s_mask[i][0], m1 = s_mask[i][1];
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const int b = s_base[i];
-    if ((m0 >> lane) & 1ull) { const int e = b + __popcll(m0 & lt); if (e < e_cap) { recv[e] = i; send[e] = lane; } }
-    if ((m1 >> lane) & 1ull) { const int e = b + __popcll(m0) + __popcll(m1 & lt); if (e < e_cap) { recv[e] = i; send[e] = lane + 64; } }
-  }
+  for (int i = wv; i < N; i += CE_THREADS / 64) gsr_rel_write_row(s_mask[i][0], s_mask[i][1], i, lane, s_base[i], e_cap, 0, recv, send);
   if (tid == 0) *count = min(total, e_cap);
   for (int e = total + tid; e < e_cap; e += CE_THREADS) { recv[e] = dummy; send[e] = dummy; }
   // the same relations as a dense rel_n x rel_n 0 / 1 matrix (what gsr_fit_bones reads): one launch less than scattering the lists into zeros
@@ -403,7 +335,7 @@ __global__ __launch_bounds__(GSR_BLOCK) void fps_multi_kernel(const float* __res
     }
     // distances are >= 0, so their bit patterns order like the values; ~index makes the smaller index the larger key
     unsigned long long key = best < 0.0f ? 0ull : (((unsigned long long)__float_as_uint(best) << 32) | (uint32_t)(~(uint32_t)besti));
-    key = ~ce_wave_min(~key);        // wave maximum on DPP (six steps + two readlanes; the 64-bit shuffle butterfly was twelve ds_bpermute trips)
+    key = ~gsr_wave_min64(~key);        // wave maximum on DPP (six steps + two readlanes; the 64-bit shuffle butterfly was twelve ds_bpermute trips)
     if (lane == 0) s_key[wv] = key;
     __syncthreads();
     if (wv == 0) {
@@ -430,7 +362,7 @@ __global__ __launch_bounds__(GSR_BLOCK) void fps_multi_kernel(const float* __res
       unsigned long long win = 0ull;
 #pragma unroll
       for (int q = 0; q < 4; ++q) if (q * 64 + lane < (int)gridDim.x) win = v[q] > win ? v[q] : win;
-      win = ~ce_wave_min(~win);
+      win = ~gsr_wave_min64(~win);
       const int nxt = (int)(~(uint32_t)win);
       if (lane < 3) s_c[lane] = pos[3 * nxt + lane];
       if (lane == 0) s_cur = nxt;

@@ -1,4 +1,4 @@
-// gsr_plan.hip -- the planner's rollout (gsdyn/plan.py; /root/reference/src/real_world/plan.py:24-154, `dynamics`): B sampled action
+// gsr_plan.hip -- the planner's rollout (gsdyn/plan.py; the reference's real_world/plan.py:24-154, `dynamics`): B sampled action
 // sequences advance B copies of one particle state through the propagation network TOGETHER.  The two kernels of gsr_gnn.hip take flat
 // row and relation lists, so B graphs laid out block-diagonally -- sample b owns the rows b R .. b R + R - 1 (R = n_obj + 1: objects, then
 // the one tool particle), one dummy row B R behind the last sample collects the padding -- are ONE graph to them.  What is new here:
@@ -7,30 +7,15 @@
 //   gsr_plan_step_tail        : clamp + add, the tool's new position, both history shifts and the look-ahead step's result.
 // No global atomics and no float reduction whose order could vary: every output is bit-identical from run to run.
 #include "gsr_common.h"
+#include "gsr_relations.h"
 
 namespace gsr_plan {
 
 // ---------------------------------------------------------------- relations of B graphs
-// The per-sample rule is construct_edges_kernel's (gsr_dynamics.hip), operation for operation: one wave per receiver, lane l holds the
-// senders l and l + 64, the k nearest objects as k successive wave minima of (distance bits << 32 | sender), a row's relations as two
-// ballots.  pm_dpp_min / pm_wave_min are COPIES of ce_dpp_min / ce_wave_min: sharing them through a header would rebuild the existing
-// dynamics code object, which this file must leave alone.
+// The per-sample rule is construct_edges_kernel's (gsr_dynamics.hip): both kernels take a row's masks, the scan of the row counts and the
+// list write from gsr_relations.h.  Own to this file: the totals across samples, the global row indices, the strided padding.
 #define PM_THREADS 1024
-#define PM_MAXK 16
 #define PR_THREADS 256
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ unsigned long long pm_dpp_min(unsigned long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)v, CTRL, ROW_MASK, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xf, false);
-  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-  return o < v ? o : v;
-}
-__device__ __forceinline__ unsigned long long pm_wave_min(unsigned long long v) {
-  v = pm_dpp_min<0xB1>(v); v = pm_dpp_min<0x4E>(v); v = pm_dpp_min<0x141>(v); v = pm_dpp_min<0x140>(v);
-  v = pm_dpp_min<0x142, 0xA>(v); v = pm_dpp_min<0x143, 0xC>(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // Launch 1, one workgroup per sample: the sample's adjacency matrix as R x 2 ballot masks and its relation total -> scratch
 // (masks [B][R][2], then totals [B], 64-bit words).
@@ -45,41 +30,11 @@ __global__ __launch_bounds__(PM_THREADS) void masks_kernel(const float* __restri
   unsigned long long* __restrict__ out = masks + (size_t)b * N * 2;
   if (tid < N) { sp[3 * tid] = pos[3 * tid]; sp[3 * tid + 1] = pos[3 * tid + 1]; sp[3 * tid + 2] = pos[3 * tid + 2]; }
   __syncthreads();
-  const int k = min(min(topk, PM_MAXK), n_valid);
+  const int k = min(min(topk, GSR_REL_MAXK), n_valid);
   int cnt = 0;                                   // (wave-uniform: the relations of this wave's rows)
   for (int i = wv; i < N; i += PM_THREADS / 64) {
-    const bool i_tool = i == n_obj_cap, i_obj = i < n_valid;
-    const float px = sp[3 * i], py = sp[3 * i + 1], pz = sp[3 * i + 2];
-    unsigned long long key[2];
-    bool near_[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = lane + 64 * h;
-      float d = __builtin_inff();
-      if (j < N) {
-        const float dx = px - sp[3 * j], dy = py - sp[3 * j + 1], dz = pz - sp[3 * j + 2];
-        d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-      }
-      near_[h] = d < thr2;
-      key[h] = j < n_valid ? (((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j) : ~0ull;   // (d >= 0: its bits order like its value)
-    }
-    unsigned long long kth = 0ull;               // the receiver's k-th nearest object as a key: k minima, each above the one before
-    bool first = true;
-    if (i_obj)
-      for (int q = 0; q < k; ++q) {
-        const unsigned long long c0 = (first || key[0] > kth) ? key[0] : ~0ull, c1 = (first || key[1] > kth) ? key[1] : ~0ull;
-        kth = pm_wave_min(c0 < c1 ? c0 : c1);
-        first = false;
-      }
     unsigned long long m[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = lane + 64 * h;
-      const bool j_tool = j == n_obj_cap, j_obj = j < n_valid;
-      bool rel = (i_obj || i_tool) && (j_tool || j_obj) && !(i_tool && j_tool) && near_[h];
-      if (i_obj && j_obj) rel = rel && key[h] <= kth;
-      m[h] = __ballot(rel);
-    }
+    gsr_rel_row_masks(sp, i, lane, N, n_obj_cap, n_valid, thr2, k, m);
     if (lane == 0) { out[2 * i] = m[0]; out[2 * i + 1] = m[1]; }
     cnt += __popcll(m[0]) + __popcll(m[1]);
   }
@@ -117,27 +72,9 @@ __global__ __launch_bounds__(PR_THREADS) void rows_kernel(int B, int n_obj_cap, 
   before = 0; all = 0;
 #pragma unroll
   for (int w = 0; w < PR_THREADS / 64; ++w) { before += s_red[0][w]; all += s_red[1][w]; }
-  if (wv == 0) {        // exclusive scan of the row counts (N <= 128: two rows per lane)
-    const int c0 = lane < N ? __popcll(s_mask[lane][0]) + __popcll(s_mask[lane][1]) : 0;
-    const int c1 = lane + 64 < N ? __popcll(s_mask[lane + 64][0]) + __popcll(s_mask[lane + 64][1]) : 0;
-    int inc0 = c0, inc1 = c1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o0 = __shfl_up(inc0, d, 64), o1 = __shfl_up(inc1, d, 64);
-      if (lane >= d) { inc0 += o0; inc1 += o1; }
-    }
-    const int tot0 = __shfl(inc0, 63, 64);
-    s_base[lane] = inc0 - c0;
-    s_base[lane + 64] = tot0 + inc1 - c1;
-  }
+  if (wv == 0) gsr_rel_scan_rows(s_mask, lane, N, s_base);
   __syncthreads();
-  for (int i = wv; i < N; i += PR_THREADS / 64) {
-    const unsigned long long m0 = s_mask[i][0], m1 = s_mask[i][1];
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
-    const int base = before + s_base[i];
-    if ((m0 >> lane) & 1ull) { const int e = base + __popcll(m0 & lt); if (e < e_cap) { recv[e] = row0 + i; send[e] = row0 + lane; } }
-    if ((m1 >> lane) & 1ull) { const int e = base + __popcll(m0) + __popcll(m1 & lt); if (e < e_cap) { recv[e] = row0 + i; send[e] = row0 + lane + 64; } }
-  }
+  for (int i = wv; i < N; i += PR_THREADS / 64) gsr_rel_write_row(s_mask[i][0], s_mask[i][1], i, lane, before + s_base[i], e_cap, row0, recv, send);
   for (int i = tid; i < N; i += PR_THREADS) row_start[row0 + i] = (long long)min(before + s_base[i], e_cap);
   for (long long e = (long long)all + (long long)b * PR_THREADS + tid; e < e_cap; e += (long long)B * PR_THREADS) { recv[e] = dummy; send[e] = dummy; }
   if (b == 0 && tid == 0) {
@@ -176,9 +113,6 @@ __global__ __launch_bounds__(GSR_BLOCK) void head_kernel(int B, int n_his, int n
   for (int c = 0; c < 3; ++c) p_in[(size_t)r * Dp + Dp - 3 + c] = tool ? eef_delta[(size_t)b * 3 + c] : 0.f;
 }
 
-// minimum that keeps a NaN (as torch.min does) and is evaluated in a fixed order
-__device__ __forceinline__ float tail_min(float a, float b) { return (b < a || b != b) ? b : a; }
-
 // One workgroup per sample, thread i = object particle i (n_obj <= 127): predicted = last + clamp(motion), the history window shifted in
 // place (a thread touches its own particle only), the look-ahead step's result for the samples whose repeat count is reached, and the
 // tool: x, y advanced by the displacement, z = the sample's lowest predicted particle (plan.py:119-122) -- LDS, then one wave's butterfly.
@@ -214,9 +148,7 @@ __global__ __launch_bounds__(PT_THREADS) void tail_kernel(int n_his, int n_obj, 
   s_z[i] = pz;
   __syncthreads();
   if (i < 64) {
-    float m = tail_min(s_z[i], s_z[i + 64]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = tail_min(m, __shfl_xor(m, off, 64));
+    const float m = gsr_wave_min_nan(gsr_min_nan(s_z[i], s_z[i + 64]));
     if (i == 0) {
       float* eb = eef_hist + (size_t)b * n_his * 3;
       const float nx = eb[3 * (n_his - 1)] + eef_delta[(size_t)b * 3], ny = eb[3 * (n_his - 1) + 1] + eef_delta[(size_t)b * 3 + 1];

@@ -4,8 +4,7 @@
 //   gsr_plan_mppi_update : the soft-max weighted push, the best sample and its reward -- one workgroup loops over B, one launch.
 // No global atomics, no float atomics.  Every float sum runs in a FIXED order (stated at each reduction), so the outputs are bit-identical
 // from run to run, and a sample's cost depends neither on B nor on the sample's position in the batch.
-// Nothing here is shared with gsr_plan.hip through a header: that would rebuild an existing code object (DESIGN.md sections 3i, 3j); the
-// NaN-keeping minimum is a copy of its tail_min.
+// The NaN-keeping minimum and its wave butterfly (gsr_min_nan, gsr_wave_min_nan: gsr_common.h) are the ones gsr_plan.hip's tail uses.
 #include "gsr_common.h"
 
 namespace gsr_pcost {
@@ -15,13 +14,6 @@ namespace gsr_pcost {
 #define PC_MAXN 1024            // particles of one sample held in LDS
 #define PC_TILE 1024            // target points per LDS tile
 
-// minimum that keeps a NaN (as torch.min does) and is evaluated in a fixed order; a maximum is pc_min of the negated values
-__device__ __forceinline__ float pc_min(float a, float b) { return (b < a || b != b) ? b : a; }
-__device__ __forceinline__ float pc_wave_min(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = pc_min(v, __shfl_xor(v, off, 64));
-  return v;
-}
 // sum of the 64 lanes as an xor butterfly, offsets 32, 16, .. 1: a fixed tree (fp addition commutes, so every lane holds the same sum)
 __device__ __forceinline__ float pc_wave_sum(float v) {
 #pragma unroll
@@ -48,7 +40,7 @@ __device__ __forceinline__ float pc_relu(float v) { return v < 0.0f ? 0.0f : v; 
 //      then the four waves' sums in wave order.
 //  The minimum runs on the squared distance, the root comes after it (monotone: the same value).  In the two pair loops the minimum is a
 //  plain v_min_f32 and the NaN travels in a sum of the (non-negative) squared distances beside it, which is NaN exactly when one of them
-//  is: one instruction instead of the three of pc_min, the same result.
+//  is: one instruction instead of the three of gsr_min_nan (gsr_common.h), the same result.
 __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int M, const float* __restrict__ state_seqs,
                                                           const float* __restrict__ actions, const float* __restrict__ state_cur,
                                                           const float* __restrict__ target, const float* __restrict__ box, float pusher,
@@ -71,13 +63,13 @@ __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int 
     float v[5] = {inf, inf, inf, inf, inf};
     for (int n = tid; n < n_obj; n += PC_THREADS) {
       const float x = src[3 * n], y = src[3 * n + 1], z = src[3 * n + 2];
-      if (coll) { const float dx = ax - x, dy = ay - y; v[0] = pc_min(v[0], dx * dx + dy * dy); }
-      if (boxed) { v[1] = pc_min(v[1], x); v[2] = pc_min(v[2], -x); v[3] = pc_min(v[3], y); v[4] = pc_min(v[4], -y); }
+      if (coll) { const float dx = ax - x, dy = ay - y; v[0] = gsr_min_nan(v[0], dx * dx + dy * dy); }
+      if (boxed) { v[1] = gsr_min_nan(v[1], x); v[2] = gsr_min_nan(v[2], -x); v[3] = gsr_min_nan(v[3], y); v[4] = gsr_min_nan(v[4], -y); }
       if (last) s_p[n] = make_float4(x, y, z, 0.0f);
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      const float r = pc_wave_min(v[k]);
+      const float r = gsr_wave_min_nan(v[k]);
       if (lane == 0) s_red[k][wv] = r;
     }
     __syncthreads();
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int 
       for (int k = 0; k < 5; ++k) {
         r[k] = s_red[k][0];
 #pragma unroll
-        for (int w = 1; w < PC_WAVES; ++w) r[k] = pc_min(r[k], s_red[k][w]);
+        for (int w = 1; w < PC_WAVES; ++w) r[k] = gsr_min_nan(r[k], s_red[k][w]);
       }
       if (coll) {
         const float c = expf(-sharp * pc_relu(sqrtf(r[0]) - pusher));
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int 
       if (boxed) {
         const float m0 = pc_relu(r[1] - box[0]), m1 = pc_relu(box[1] + r[2]), m2 = pc_relu(r[3] - box[2]), m3 = pc_relu(box[3] + r[4]);
         float e = -expf(-sharp * m0);                            // the largest of the four as a NaN-keeping minimum of the negated
-        e = pc_min(e, -expf(-sharp * m1)); e = pc_min(e, -expf(-sharp * m2)); e = pc_min(e, -expf(-sharp * m3));
+        e = gsr_min_nan(e, -expf(-sharp * m1)); e = gsr_min_nan(e, -expf(-sharp * m2)); e = gsr_min_nan(e, -expf(-sharp * m3));
         box_pen[(size_t)b * T + t] = -e;
         bsum += -e;
       }
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int 
           m = fminf(m, d);
           nan_acc += d;
         }
-        s_min[slice * GN + n] = pc_min(s_min[slice * GN + n], nan_acc != nan_acc ? nan_acc : m);
+        s_min[slice * GN + n] = gsr_min_nan(s_min[slice * GN + n], nan_acc != nan_acc ? nan_acc : m);
       }
     }
   }
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(PC_THREADS) void cost_kernel(int T, int n_obj, int 
   float sum_b = 0.0f;
   for (int n = tid; n < n_obj; n += PC_THREADS) {
     float m = s_min[n];
-    for (int s = 1; s < S; ++s) m = pc_min(m, s_min[s * GN + n]);
+    for (int s = 1; s < S; ++s) m = gsr_min_nan(m, s_min[s * GN + n]);
     sum_b += sqrtf(m);
   }
   sum_a = pc_wave_sum(sum_a);

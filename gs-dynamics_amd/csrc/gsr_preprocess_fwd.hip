@@ -9,17 +9,10 @@
 // (+48 M-coefficient SH when used), writes 48 (record) + 8 (rect) + 4 (tiles) + 4 (clamp) + 4 (radii) = 68 B.
 // The 4x4 matrices are read through uniform (scalar) loads: they never occupy VGPRs.
 #include "gsr_common.h"
+#include "gsr_sh.h"
 
 // kernels live in a NAMED namespace: profilers and traces show gsr_preprocess_fwd::<kernel>, not "(anonymous namespace)"
 namespace gsr_preprocess_fwd {
-
-__constant__ float kC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                             -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                             0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
-                             -0.5900435899266435f};
-#define SH_C0 0.28209479177387814f
-#define SH_C1 0.4886025119029199f
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

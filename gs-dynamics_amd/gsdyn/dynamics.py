@@ -257,18 +257,7 @@ class DynamicsPredictor(nn.Module):
         """state_t [N, n_his * 3], attributes a [N, attr_dim], instance column g [N, 1], action act [N, action_dim], relations as index
         vectors [E] -> (predicted positions, motions) of ALL N rows (the caller keeps the object particles)."""
         c = self.model_config
-        N, n_his = a.shape[0], c["n_his"]
-        parts = [a]
-        if c["state_dim"] == 3:
-            parts.append(state_t)
-        elif c["state_dim"] == 1:
-            parts.append(state_t.view(N, n_his, 3)[..., 2])
-        if self.motion_dim > 0:
-            s4 = state_t.view(N, n_his, 3)
-            parts.append((s4[:, 1:] - s4[:, :-1]).reshape(N, (n_his - 1) * 3))
-        if c["action_dim"] > 0:
-            parts.append(act)
-        p_inputs = torch.cat(parts, 1)
+        p_inputs = self._particle_inputs(state_t, a, act)
         both = torch.cat([a, g, state_t], 1)                                  # one gather per side for the three relation features
         br, bs = both[receivers], both[senders]
         na, ng = a.shape[1], g.shape[1]
