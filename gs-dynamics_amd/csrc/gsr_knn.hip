@@ -41,6 +41,7 @@
 // count u32[M] | end u32[M] | slot u32[N] | sorted float4[N].  info[i] = shells walked | 0x80000000 if the brute-force pass finished row i
 // (read by tools/knn_cost.py through _hip.knn(stats=True)).
 #include "gsr_common.h"
+#include "gsr_hashgrid.h"
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -55,7 +56,7 @@ namespace gsr_knn_ns {
 #define KNN_SAMPLES 256
 #define KNN_MAXR 3           // shells before a query is handed to the brute-force pass: 27 + 98 + 218 cells
 #define KNN_MAXG (1 << 20)
-#define KNN_EMPTY 0xffffffffffffffffull
+#define KNN_EMPTY GSR_HASH_EMPTY
 #define KNN_FLAG 0x80000000u
 
 struct KnnHeader {           // 256 bytes of device memory at the front of the scratch
@@ -184,10 +185,6 @@ __device__ __forceinline__ int knn_cell(float p, float o, float inv_h, int G) {
 __device__ __forceinline__ unsigned long long knn_key(int cx, int cy, int cz) {
   return ((unsigned long long)cx << 40) | ((unsigned long long)cy << 20) | (unsigned long long)cz;
 }
-__device__ __forceinline__ uint32_t knn_hash(unsigned long long x, uint32_t mask) {   // the 64-bit finaliser of MurmurHash3
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return (uint32_t)x & mask;
-}
 
 // One workgroup: bounding box, the median of the samples, the header.
 #define KNN_SETUP_THREADS 1024
@@ -264,12 +261,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_insert_kernel(int N, const fl
   const float inv_h = hdr->inv_h;
   const unsigned long long key = knn_key(knn_cell(pts[3 * (size_t)i], hdr->ox, inv_h, hdr->gx), knn_cell(pts[3 * (size_t)i + 1], hdr->oy, inv_h, hdr->gy),
                                          knn_cell(pts[3 * (size_t)i + 2], hdr->oz, inv_h, hdr->gz));
-  uint32_t s = knn_hash(key, mask);
-  for (uint32_t probe = 0; probe <= mask; ++probe) {     // at most N <= M / 2 distinct keys: an empty slot always turns up
-    const unsigned long long old = atomicCAS(&keys[s], KNN_EMPTY, key);
-    if (old == KNN_EMPTY || old == key) break;
-    s = (s + 1) & mask;
-  }
+  const uint32_t s = gsr_hash_insert(keys, mask, key);   // (gsr_hashgrid.h) at most N <= M / 2 distinct keys: an empty slot always turns up
   atomicAdd(&cnt[s], 1u);
   slot[i] = s;
 }
@@ -328,7 +320,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_grid_kernel(int N, int k, int
         const int x = cqx + dx, y = cqy + dy, z = cqz + dz;
         if ((r == 1 || m == r) && x >= 0 && x < gx && y >= 0 && y < gy && z >= 0 && z < gz) {
           const unsigned long long key = knn_key(x, y, z);
-          uint32_t s = knn_hash(key, mask);
+          uint32_t s = gsr_hash64(key, mask);
           for (uint32_t probe = 0; probe <= mask; ++probe) {
             const unsigned long long kk = keys[s];
             if (kk == key) { count = cnt[s]; start = endp[s] - count; break; }

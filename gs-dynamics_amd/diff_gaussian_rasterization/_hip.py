@@ -95,7 +95,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
            "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
            "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update",
-           "gsr_knn_scratch_bytes", "gsr_knn")
+           "gsr_knn_scratch_bytes", "gsr_knn",
+           "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views")
 
 
 def load_library():
@@ -232,6 +233,12 @@ def load_library():
     lib.gsr_knn_scratch_bytes.restype = sz; lib.gsr_knn_scratch_bytes.argtypes = [i32]
     lib.gsr_knn.restype = C.c_int
     lib.gsr_knn.argtypes = [i32, vp, i32, i32, vp, vp, vp, vp]
+    F3 = C.POINTER(C.c_float)
+    lib.gsr_voxel_scratch_bytes.restype = sz; lib.gsr_voxel_scratch_bytes.argtypes = [i32, F3, F3, C.c_float]
+    lib.gsr_voxel_points.restype = C.c_int
+    lib.gsr_voxel_points.argtypes = [i32, vp, vp, F3, F3, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.gsr_voxel_depth_views.restype = C.c_int
+    lib.gsr_voxel_depth_views.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, F3, F3, C.c_float, C.c_float, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1304,6 +1311,75 @@ def knn(points: torch.Tensor, k: int, exclude_self: bool = False, stats: bool = 
                   mean_shells=float((info & 0xff)[grid_rows].float().mean().item()) if bool(grid_rows.any()) else float(KNN_MAX_SHELLS),
                   cells=tuple(g), occupied=occupied, h=float(hdr[48:52].view(torch.float32).item()), per_cell=N / max(occupied, 1))
     return idx, d2, st
+
+
+VOXEL_MAX_N = 1 << 24    # csrc/gsr_voxel.hip VOX_MAX_N: u32 colour sums and int64 offset sums cannot overflow up to here
+
+
+def _voxel_call(who, dev, N, lo, hi, inv_h, cap, with_colors, launch):
+    """The part the two voxel entry points share: the box as host floats, scratch and capacity-sized outputs, the launch, the 4-byte
+    read-back of M, the rows cut to M (copied when that frees memory worth the copy)."""
+    lib = load_library()
+    lo3, hi3 = (C.c_float * 3)(*[float(x) for x in lo]), (C.c_float * 3)(*[float(x) for x in hi])
+    N, cap = int(N), int(cap)
+    if not 1 <= N <= VOXEL_MAX_N:
+        raise ValueError(f"{who}: 1 <= N <= 2^24, please (got {N})")
+    nbytes = int(lib.gsr_voxel_scratch_bytes(N, lo3, hi3, float(inv_h)))
+    if nbytes == 0 or cap < 1:
+        raise ValueError(f"{who}: a box lo <= hi with fewer than 2^21 - 1 cells per axis and cap >= 1, please")
+    with _on(dev):
+        scratch = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+        pad = (-scratch.data_ptr()) % 256
+        pts = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+        col = torch.empty((cap, 3), dtype=torch.float32, device=dev) if with_colors else None
+        cnt = torch.empty((cap,), dtype=torch.int32, device=dev)
+        first = torch.empty((cap,), dtype=torch.int64, device=dev)
+        m_dev = torch.empty((1,), dtype=torch.int32, device=dev)
+        _check(launch(lib, lo3, hi3, C.c_void_p(scratch.data_ptr() + pad), cap, _ptr(pts), _ptr(col), _ptr(cnt), _ptr(first), _ptr(m_dev), _stream(dev)), who)
+        m = int(m_dev.item())
+        cut = (lambda t: t[:m].clone()) if 2 * m < cap else (lambda t: t[:m])
+        return cut(pts), (cut(col) if with_colors else None), cut(cnt), cut(first)
+
+
+def _voxel_colors_ok(colors, N, dev, who):
+    if colors is not None and not (colors.is_contiguous() and colors.dtype == torch.uint8 and colors.device == dev and colors.numel() == 3 * N):
+        raise ValueError(f"{who}: colors must be a contiguous uint8 tensor of N x 3 entries on the points' device")
+
+
+def voxel_points(points: torch.Tensor, lo, hi, inv_h: float, cap: int, colors: Optional[torch.Tensor] = None):
+    """gsr_voxel_points (include/gsr.h): points [N, 3] fp32, colors [N, 3] uint8 or None, the box ``lo`` / ``hi`` (three host floats each),
+    inv_h = fl32(1 / voxel size), cap >= min(N, cells of the box) -> (points [M, 3], colors [M, 3] or None, counts [M] int32, first [M]
+    int64), rows ascending in ``first``.  One 4-byte read-back, for M."""
+    _require_device(points)
+    dev = points.device
+    if not (points.is_contiguous() and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3):
+        raise ValueError("voxel_points: a contiguous float32 [N, 3] tensor, please")
+    N = int(points.shape[0])
+    _voxel_colors_ok(colors, N, dev, "voxel_points")
+    return _voxel_call("gsr_voxel_points", dev, N, lo, hi, inv_h, cap, colors is not None,
+                       lambda lib, lo3, hi3, scratch, cap, *outs: lib.gsr_voxel_points(N, _ptr(points), _ptr(colors), lo3, hi3, float(inv_h), scratch, cap, *outs))
+
+
+def voxel_depth_views(depths: torch.Tensor, K4: torch.Tensor, R: torch.Tensor, t: torch.Tensor, lo, hi, depth_lo: float, depth_hi: float, inv_h: float,
+                      cap: int, colors: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None):
+    """gsr_voxel_depth_views (include/gsr.h): depths [V, H, W] fp32, K4 [V, 4] = (fx, fy, cx, cy), R [V, 3, 3], t [V, 3], colors [V, H, W, 3]
+    uint8 or None, masks [V, H, W] bool / uint8 or None -> as ``voxel_points``, ``first`` = the flat pixel index.  One fused kernel over the
+    pixels (the world cloud is never written), one 4-byte read-back, for M."""
+    _require_device(depths)
+    dev = depths.device
+    if not (depths.is_contiguous() and depths.dtype == torch.float32 and depths.dim() == 3):
+        raise ValueError("voxel_depth_views: depths must be a contiguous float32 [V, H, W] tensor")
+    V, H, W = (int(x) for x in depths.shape)
+    N = V * H * W
+    for x, shape, name in ((K4, (V, 4), "K4"), (R, (V, 3, 3), "R"), (t, (V, 3), "t")):
+        if not (x.is_contiguous() and x.dtype == torch.float32 and x.device == dev and tuple(x.shape) == shape):
+            raise ValueError(f"voxel_depth_views: {name} must be a contiguous float32 {list(shape)} tensor on the depths' device")
+    _voxel_colors_ok(colors, N, dev, "voxel_depth_views")
+    if masks is not None and not (masks.is_contiguous() and masks.dtype in (torch.bool, torch.uint8) and masks.device == dev and masks.numel() == N):
+        raise ValueError("voxel_depth_views: masks must be a contiguous bool or uint8 [V, H, W] tensor on the depths' device")
+    return _voxel_call("gsr_voxel_depth_views", dev, N, lo, hi, inv_h, cap, colors is not None,
+                       lambda lib, lo3, hi3, scratch, cap, *outs: lib.gsr_voxel_depth_views(V, H, W, _ptr(depths), _ptr(K4), _ptr(R), _ptr(t), _ptr(colors), _ptr(masks),
+                                                                                            lo3, hi3, float(depth_lo), float(depth_hi), float(inv_h), scratch, cap, *outs))
 
 
 def fps_thin(pos: torch.Tensor, npoints: int, radius: float, start_idx: int = 0, thin_start_idx: int = 0):

@@ -11,4 +11,5 @@ from .step import params2rendervar, get_loss, get_loss_views, loss_and_grads_vie
 from .plan import (decode_action, rollout_actions, running_cost, mppi_update, sample_action_seq, clip_actions,  # noqa: F401
                    plan_actions)
 from .knn import knn_points  # noqa: F401
+from .observe import voxel_down_sample, depth_to_cloud, observe_state  # noqa: F401
 from .train import train, train_timestep, initialize_per_timestep, initialize_post_first_timestep, params2cpu, save_params  # noqa: F401

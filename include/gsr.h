@@ -592,6 +592,32 @@ int gsr_plan_mppi_update(int32_t B, int32_t T, const float* act_seqs, const floa
  * 1 <= N <= 2^28, 1 <= k <= 64, k <= N - (exclude_self ? 1 : 0), no NULL pointer: -2 and no launch otherwise. */
 size_t gsr_knn_scratch_bytes(int32_t N); /* host-only */
 int gsr_knn(int32_t N, const float* points, int32_t k, int32_t exclude_self, void* scratch, int64_t* out_idx, float* out_d2, void* stream);
+/* ---- depth cameras / a point cloud -> one mean point per occupied voxel (csrc/gsr_voxel.hip; gsdyn.depth_to_cloud,
+ * gsdyn.voxel_down_sample).  Additive to ABI 125.  One right answer, bit for bit; every operation below is fp32 and unfused unless it says fp64.
+ * Unprojection (gsr_voxel_depth_views): pixel (x, y) of view v with depth d, K4[v] = (fx, fy, cx, cy), R[v] row-major [3, 3], t[v] (camera to
+ *   board):  xc = ((x - cx) * (1 / fx)) * d,  yc = ((y - cy) * (1 / fy)) * d,  zc = d,  w_i = ((R[i][0] xc + R[i][1] yc) + R[i][2] zc) + t[i].
+ *   The pixel is kept if depth_lo < d < depth_hi (both strict: a NaN and a zero drop out), its mask byte is non-zero (masks == NULL: all
+ *   kept) and lo[i] <= w_i <= hi[i] on every axis.  Its input index is (v H + y) W + x.
+ *   gsr_voxel_points takes points[i] in place of w and keeps the rows inside the box (a NaN or an infinity is inside no box).
+ * Voxel: u = fl(fl(w - lo) * inv_h) per axis, cell c = floor(u), offset f = u - c (exact).  The origin is the box's lower corner.
+ *   (hi - lo) * inv_h must be below 2^21 - 1 on every axis: the key is three 21-bit cells.
+ * Mean: q = int64(f * 2^32), S = the integer sum of q over the voxel's n members (independent of order),
+ *   out_points = fl32((c + S / (n 2^32)) * (1 / inv_h) + lo) evaluated in fp64;  out_colors = fl32(sum of the uint8 channel / (255 n)), in fp64;
+ *   out_counts = n;  out_first = the lowest input index among the members.  Rows ascend in out_first.  *out_m = the number of rows M.
+ * Integer sums only: bit-identical from call to call and for every order of the input (as a set of rows).
+ * colors: [N, 3] uint8 or NULL (then out_colors must be NULL).  lo, hi: HOST pointers to three floats.  Everything else lives on the device.
+ * The outputs hold `cap` rows, cap >= min(N, cells of the box); cells per axis = floor((hi - lo) * inv_h) + 1.  No row beyond cap is written.
+ * scratch: gsr_voxel_scratch_bytes bytes on the device, 256-byte aligned, contents neither needed nor kept (a hash table of 2 min(N, cells)
+ * slots rounded up to a power of two, never a dense array over the box; returns 0 for arguments the calls reject).
+ * No host read-back and no synchronisation: everything runs on `stream`; the caller reads *out_m.
+ * 1 <= N = V H W <= 2^24 (u32 colour sums and int64 offset sums cannot overflow), a box lo <= hi, 0 < inv_h < inf, no NULL pointer other
+ * than colors / masks / out_colors: -2 and no launch otherwise. */
+size_t gsr_voxel_scratch_bytes(int32_t N, const float* lo, const float* hi, float inv_h); /* host-only */
+int gsr_voxel_points(int32_t N, const float* points, const uint8_t* colors, const float* lo, const float* hi, float inv_h, void* scratch, int32_t cap,
+                     float* out_points, float* out_colors, int32_t* out_counts, int64_t* out_first, int32_t* out_m, void* stream);
+int gsr_voxel_depth_views(int32_t V, int32_t H, int32_t W, const float* depths, const float* K4, const float* R, const float* t, const uint8_t* colors,
+                          const uint8_t* masks, const float* lo, const float* hi, float depth_lo, float depth_hi, float inv_h, void* scratch, int32_t cap,
+                          float* out_points, float* out_colors, int32_t* out_counts, int64_t* out_first, int32_t* out_m, void* stream);
 int gsr_fps(int32_t N, const float* pos, int32_t npoints, int32_t start_idx, float* scratch, int64_t* out_idx, void* stream);
 int gsr_lbs(int32_t P, int32_t n_bones, const float* bones, const float* rotations, const float* translations,
             const float* bone_quats, const float* xyz, const float* quat, float* out_xyz, float* out_quat, void* stream);
