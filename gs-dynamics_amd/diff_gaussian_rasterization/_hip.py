@@ -96,7 +96,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
            "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update",
            "gsr_knn_scratch_bytes", "gsr_knn",
-           "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views")
+           "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views",
+           "gsr_gnn_aggregate_backward", "gsr_gnn_rel_inputs_backward")
 
 
 def load_library():
@@ -212,6 +213,10 @@ def load_library():
     lib.gsr_gnn_rel_inputs.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.gsr_gnn_aggregate_res.restype = C.c_int
     lib.gsr_gnn_aggregate_res.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsr_gnn_aggregate_backward.restype = C.c_int
+    lib.gsr_gnn_aggregate_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsr_gnn_rel_inputs_backward.restype = C.c_int
+    lib.gsr_gnn_rel_inputs_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.gsr_construct_edges_rows.restype = C.c_int
     lib.gsr_construct_edges_rows.argtypes = [vp, i32, vp, C.c_float, i32, C.c_int64, i32, vp, vp, vp, vp, i32, vp, vp]
     lib.gsr_rollout_step_head.restype = C.c_int
@@ -1468,6 +1473,64 @@ def gnn_aggregate(rel_part: torch.Tensor, node_parts: torch.Tensor, senders: tor
             return agg, out
         _check(lib.gsr_gnn_aggregate(N, n_sum, H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(row_start), _ptr(agg), _stream(dev)), "gsr_gnn_aggregate")
     return agg
+
+
+def gnn_aggregate_backward(rel_part: torch.Tensor, node_parts: torch.Tensor, senders: torch.Tensor, receivers: torch.Tensor, row_start: torch.Tensor,
+                           rev_ptr: torch.Tensor, rev_edge: torch.Tensor, d_agg: torch.Tensor, n_sum_rows: int = None):
+    """gsr_gnn_aggregate_backward: the inputs of ``gnn_aggregate`` plus receivers [E], the sender-side reverse list rev_ptr [N + 1] /
+    rev_edge [E] (relation ids stably sorted by sender) and d_agg [N, H] -> (d_rel_part [E, H], d_node_parts [N, 2 H]).  With z[e] =
+    (rel_part[e] + node_parts[recv, :H]) + node_parts[send, H:] recomputed as the forward forms it and m[e] = 0 where z[e] <= 0 or recv
+    >= n_sum_rows, d_agg[recv] otherwise (a NaN z passes, as torch's threshold_backward): d_rel_part[e] = m[e]; d_node_parts[i, :H] = the
+    sum of m over i's segment in list order; d_node_parts[i, H:] = the sum of m over i's reverse list in ascending e.  No atomics:
+    bit-identical from run to run.  Contracts as ``gnn_aggregate`` (ValueError); E = 0: zeros, no library call."""
+    _gnn_f32("gnn_aggregate_backward", rel_part=rel_part, node_parts=node_parts, d_agg=d_agg)
+    _require_device(rel_part)
+    lib = load_library()
+    dev = rel_part.device
+    N, E, H = int(node_parts.shape[0]), int(rel_part.shape[0]), int(rel_part.shape[1])
+    if H <= 0 or H % 4 != 0 or int(node_parts.shape[1]) != 2 * H or node_parts.device != dev or tuple(d_agg.shape) != (N, H) or d_agg.device != dev:
+        raise ValueError("gnn_aggregate_backward: rel_part [E, H], node_parts [N, 2 H] and d_agg [N, H] on one device with H a multiple of 4, please")
+    _gnn_index("gnn_aggregate_backward", dev, E, senders=senders, receivers=receivers, rev_edge=rev_edge)
+    _gnn_index("gnn_aggregate_backward", dev, N + 1, row_start=row_start, rev_ptr=rev_ptr)
+    n_sum = N if n_sum_rows is None else int(n_sum_rows)
+    if not 0 <= n_sum <= N:
+        raise ValueError("gnn_aggregate_backward: n_sum_rows must lie in [0, N]")
+    with _on(dev):
+        if E == 0 or N == 0:
+            return torch.zeros((E, H), dtype=torch.float32, device=dev), torch.zeros((N, 2 * H), dtype=torch.float32, device=dev)
+        # the relations of rows >= n_sum get no gradient and no thread: their rows are zeroed here
+        d_rel = (torch.empty if n_sum == N else torch.zeros)((E, H), dtype=torch.float32, device=dev)
+        d_nodes = torch.empty((N, 2 * H), dtype=torch.float32, device=dev)
+        _check(lib.gsr_gnn_aggregate_backward(N, n_sum, H, _ptr(rel_part), _ptr(node_parts), _ptr(senders), _ptr(receivers), _ptr(row_start), _ptr(rev_ptr),
+                                              _ptr(rev_edge), _ptr(d_agg), _ptr(d_rel), _ptr(d_nodes), _stream(dev)), "gsr_gnn_aggregate_backward")
+    return d_rel, d_nodes
+
+
+def gnn_rel_inputs_backward(d_out: torch.Tensor, row_start: torch.Tensor, rev_ptr: torch.Tensor, rev_edge: torch.Tensor, attr_dim: int,
+                            state_cols: int) -> torch.Tensor:
+    """gsr_gnn_rel_inputs_backward: d_out [E, 2 attr_dim + 1 + state_cols] (the gradient of ``gnn_rel_inputs``' result), the receiver
+    segments row_start [N + 1] and the sender-side reverse list rev_ptr [N + 1] / rev_edge [E] -> d_state [N, state_cols]: per column the
+    list-order fp32 sum over the node's segment minus the ascending-e fp32 sum over its reverse list.  The attribute and instance columns
+    get no gradient.  Contracts as ``gnn_rel_inputs`` (ValueError); state_cols = 0 or E = 0: zeros, no library call."""
+    _gnn_f32("gnn_rel_inputs_backward", d_out=d_out)
+    _require_device(d_out)
+    lib = load_library()
+    dev = d_out.device
+    A, S, E = int(attr_dim), int(state_cols), int(d_out.shape[0])
+    if A < 0 or S < 0 or int(d_out.shape[1]) != 2 * A + 1 + S:
+        raise ValueError("gnn_rel_inputs_backward: d_out must be [E, 2 attr_dim + 1 + state_cols]")
+    N = int(row_start.shape[0]) - 1 if row_start.dim() == 1 else -1
+    if N < 0:
+        raise ValueError("gnn_rel_inputs_backward: row_start must be a vector of N + 1 entries")
+    _gnn_index("gnn_rel_inputs_backward", dev, N + 1, row_start=row_start, rev_ptr=rev_ptr)
+    _gnn_index("gnn_rel_inputs_backward", dev, E, rev_edge=rev_edge)
+    with _on(dev):
+        if S == 0 or E == 0 or N == 0:
+            return torch.zeros((N, S), dtype=torch.float32, device=dev)
+        d_state = torch.empty((N, S), dtype=torch.float32, device=dev)
+        _check(lib.gsr_gnn_rel_inputs_backward(N, A, S, _ptr(d_out), _ptr(row_start), _ptr(rev_ptr), _ptr(rev_edge), _ptr(d_state), _stream(dev)),
+               "gsr_gnn_rel_inputs_backward")
+    return d_state
 
 
 def fit_bones(bones: torch.Tensor, motions: torch.Tensor, relations: torch.Tensor, out=None):

@@ -1,0 +1,128 @@
+"""Fitting the propagation network -- the training loop body of the reference's third program (its src/train.py:171-220) as two
+functions: ``dynamics_loss`` (the ``n_future`` predictions of one batch, each written into the next step's history, with the mse and
+relation-length terms) and ``train_dynamics_step`` (zero_grad, loss, backward, optimiser step).
+
+Two paths compute the same loss.  The DEFINITION is ``DynamicsPredictor.forward`` under autograd on the dataset's dense ``Rr`` / ``Rs``.
+The DEVICE path (float32 on a HIP device) turns the B graphs of a batch into one block-diagonal index-form graph -- node ids offset by
+b N, padded relations dropped, relations stably sorted by receiver, built ONCE per batch -- and runs ``propagate_split_grad``: the split
+propagation with kernels for the two steps between the matrix products, forward and backward.  Its gradients are sums in a fixed order
+(no atomics) and bit-identical from run to run; the eager path's scatter_add / index backward are not.
+
+``DEVICE_PATH_DEFAULT`` is what ``device_path=None`` means; DESIGN.md section 3m has the measurement that decided it.
+Out of scope here: rigid_loss / Umeyama, l1_loss, the dataset and its loader, checkpoints, plots."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import torch
+
+from .dynamics import DynamicsPredictor, _GnnRelInputs, split_graph
+
+DEVICE_PATH_DEFAULT = True          # measured 1.3 - 3.6 x faster per training step than the eager path (profiles/gnn_train_cost.txt)
+
+
+def _device_path_ok(model: DynamicsPredictor, batch: Dict) -> bool:
+    state, attrs, inst = batch["state"], batch["attrs"], batch["p_instance"]
+    if not (state.is_cuda and state.dtype == torch.float32 and attrs.dtype == torch.float32 and model.split_grad_ok(attrs)):
+        return False
+    if attrs.requires_grad or inst.requires_grad or batch["Rr"].dtype != torch.float32:
+        return False
+    return all(p.device == state.device and p.dtype == torch.float32 for p in model.parameters())
+
+
+def _length_term(d_pred, d_pos, denom):
+    """mse between the relations' lengths after and before the step; ``denom`` = B n_rel, the padded rows included (their lengths are 0
+    on both sides), as the dense formula divides."""
+    return ((d_pred.norm(dim=-1) - d_pos.norm(dim=-1)) ** 2).sum() / denom
+
+
+def _next_history(state, pred, tool_next):
+    """The history one step on: the prediction for the object particles, the recorded rows for the tools (a new tensor)."""
+    n_p = pred.shape[1]
+    return torch.cat([state[:, 1:], torch.cat([pred, tool_next[:, n_p:]], 1)[:, None]], 1)
+
+
+def _eager_loss(model, batch, n_future, mse_weight, length_weight):
+    state, action = batch["state"], batch.get("action")
+    Rr, Rs = batch["Rr"], batch["Rs"]
+    B, n_rel, N = Rr.shape
+    recv, send, w = model._indices(Rr, Rs)
+    bidx = torch.arange(B, device=state.device)[:, None]
+    terms = [0.0, 0.0]
+    for fi in range(n_future):
+        gt = batch["state_future"][:, fi]
+        n_p = gt.shape[1]
+        pred = model(state=state, attrs=batch["attrs"], p_instance=batch["p_instance"], action=action, Rr=Rr, Rs=Rs)[0][:, :n_p]
+        # a relation's end at a tool row (>= n_p) counts as the origin, as in the dense product with Rr[:, :, :n_p]
+        ext = lambda x: torch.cat([x, x.new_zeros((B, N - n_p, 3))], 1)  # noqa: E731
+        diff = lambda x: (x[bidx, recv] - x[bidx, send]) * w[..., None]  # noqa: E731
+        terms[0] = terms[0] + mse_weight * torch.nn.functional.mse_loss(pred, gt)
+        terms[1] = terms[1] + length_weight * _length_term(diff(ext(pred)), diff(ext(state[:, 0, :n_p].detach())), B * n_rel)
+        if fi < n_future - 1:
+            state, action = _next_history(state, pred, batch["tool_future"][:, fi]), batch["action_future"][:, fi]
+    return terms
+
+
+def _device_loss(model, batch, n_future, mse_weight, length_weight):
+    c = model.model_config
+    state, action, attrs, inst = batch["state"], batch.get("action"), batch["attrs"], batch["p_instance"]
+    Rr, Rs = batch["Rr"], batch["Rs"]
+    B, n_rel, N = Rr.shape
+    dev, n_his = state.device, state.shape[1]
+    # ---- the batch's graphs as one block-diagonal graph, once (the relations do not change over the n_future steps)
+    recv, send, w = model._indices(Rr, Rs)
+    b, r = torch.nonzero(w > 0, as_tuple=True)                   # the one host read of the batch: the relation count
+    recv, order = torch.sort(recv[b, r] + b * N, stable=True)    # batch-major already; within a receiver the dataset's row order stays
+    graph = split_graph(recv, (send[b, r] + b * N)[order], B * N)
+    a = attrs.reshape(B * N, attrs.shape[2]).contiguous()
+    g = torch.cat([inst, inst.new_zeros((B, N - inst.shape[1], inst.shape[2]))], 1).reshape(B * N, inst.shape[2]).contiguous()
+    none = a.new_zeros((B * N, 0))
+    terms = [0.0, 0.0]
+    for fi in range(n_future):
+        gt = batch["state_future"][:, fi]
+        n_p = gt.shape[1]
+        state_t = state.transpose(1, 2).reshape(B * N, n_his * 3)
+        act = action.reshape(B * N, action.shape[2]).contiguous() if c["action_dim"] > 0 else none
+        pos = model.propagate_split_grad(state_t, a, g, act, graph)[0].view(B, N, 3)
+        pred = pos[:, :n_p]
+        obj = torch.zeros((1, N, 1), dtype=pos.dtype, device=dev)
+        obj[:, :n_p] = 1.0
+        # the relations' difference vectors through the relation-input kernel (no attributes, no instances, three "state" columns): its
+        # backward is the fixed-order walk, where a row gather's would be an index_add with atomics
+        d_pred = _GnnRelInputs.apply(none, none, (pos * obj).reshape(B * N, 3), graph)[:, 1:]
+        pos0 = (state[:, 0].detach() * obj).reshape(B * N, 3)
+        terms[0] = terms[0] + mse_weight * torch.nn.functional.mse_loss(pred, gt)
+        terms[1] = terms[1] + length_weight * _length_term(d_pred, pos0[graph.receivers] - pos0[graph.senders], B * n_rel)
+        if fi < n_future - 1:
+            state, action = _next_history(state, pred, batch["tool_future"][:, fi]), batch["action_future"][:, fi]
+    return terms
+
+
+def dynamics_loss(model: DynamicsPredictor, batch: Dict, *, n_future: int, mse_weight: float = 1.0, length_weight: float = 0.01,
+                  device_path: Optional[bool] = None) -> Tuple[torch.Tensor, Dict]:
+    """The training loss of one batch of the reference's dataset dictionary: ``state`` [B, n_his, N, 3], ``attrs`` [B, N, attr_dim],
+    ``p_instance`` [B, n_p, G], ``action`` [B, N, 3], dense ``Rr`` / ``Rs`` [B, n_rel, N] (all-zero rows are padding), ``state_future``
+    [B, >= n_future, n_p, 3], ``tool_future`` / ``action_future`` [B, >= n_future - 1, N, 3].  ``n_future`` predictions; each becomes the
+    newest frame of the next step's history (the tools' rows from ``tool_future``, the action from ``action_future``); every step adds
+    mse_weight x mse(prediction, state_future) + length_weight x mse of the relations' lengths against the oldest history frame.  The
+    caller's tensors are not modified.  -> (loss, dict(mse=, length= the weighted sums over the steps, detached; device_path= bool)).
+
+    ``device_path``: True asks for the kernels' path, False for plain ``model.forward`` under autograd, None for ``DEVICE_PATH_DEFAULT``.
+    The kernels' path is taken only for float32 tensors on a HIP device with a configuration the split propagation accepts and attributes
+    / instances that need no gradient; everything else runs ``model.forward``, which is also the definition."""
+    n_future = int(n_future)
+    if n_future < 1:
+        raise ValueError("dynamics_loss: n_future must be at least 1")
+    want = DEVICE_PATH_DEFAULT if device_path is None else bool(device_path)
+    use = want and _device_path_ok(model, batch)
+    mse, length = (_device_loss if use else _eager_loss)(model, batch, n_future, float(mse_weight), float(length_weight))
+    return mse + length, dict(mse=mse.detach(), length=length.detach(), device_path=use)
+
+
+def train_dynamics_step(model: DynamicsPredictor, optimizer, batch: Dict, **kw) -> torch.Tensor:
+    """One optimisation step on one batch: zero_grad, ``dynamics_loss(model, batch, **kw)``, backward, step.  -> the loss (detached)."""
+    optimizer.zero_grad()
+    loss, _ = dynamics_loss(model, batch, **kw)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import os
 
-from typing import Optional, Dict, Tuple
+from typing import NamedTuple, Optional, Dict, Tuple
 
 import numpy as np
 import torch
@@ -160,6 +160,67 @@ class _Head(nn.Module):      # parameters ``linear_0/1/2``
 
     def forward(self, x):
         return self.linear_2(_linear_relu(self.linear_1, _linear_relu(self.linear_0, x)))
+
+
+class SplitGraph(NamedTuple):
+    """One relation list, ascending in the receiver, with what the split propagation's kernels and their backward walk (all int64)."""
+    receivers: torch.Tensor      # [E]
+    senders: torch.Tensor        # [E]
+    row_start: torch.Tensor      # [N + 1]: row i receives the relations row_start[i] .. row_start[i + 1] - 1
+    rev_ptr: torch.Tensor        # [N + 1]: row i sends the relations rev_edge[rev_ptr[i] .. rev_ptr[i + 1] - 1]
+    rev_edge: torch.Tensor       # [E]: the relation ids stably sorted by sender (ids ascend within a sender)
+
+
+def split_graph(receivers: torch.Tensor, senders: torch.Tensor, n_rows: int) -> SplitGraph:
+    """The segment bounds and the sender-side reverse list of a relation list that ASCENDS in the receiver -- built once per graph (no
+    host read), shared by every propagation step and every call that keeps the relations (``losses.reverse_adjacency``'s sorting idiom,
+    in the int64 the GNN wrappers take)."""
+    receivers, senders = receivers.to(torch.int64).contiguous(), senders.to(torch.int64).contiguous()
+    row_start = torch.searchsorted(receivers, torch.arange(n_rows + 1, device=receivers.device, dtype=torch.int64))
+    order = torch.argsort(senders, stable=True)
+    rev_ptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=receivers.device)
+    rev_ptr[1:] = torch.cumsum(torch.bincount(senders, minlength=n_rows), 0)
+    return SplitGraph(receivers, senders, row_start.contiguous(), rev_ptr, order.contiguous())
+
+
+class _GnnRelInputs(torch.autograd.Function):
+    """gsr_gnn_rel_inputs with its gradient toward the state columns (gsr_gnn_rel_inputs_backward).  Attributes and instance columns are
+    constants of the dataset: asking for their gradient is an error, not a silent zero."""
+
+    @staticmethod
+    def forward(ctx, a, g, state_t, graph):
+        from diff_gaussian_rasterization import _hip
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            raise RuntimeError("the device path has no gradient toward attributes or instances: use DynamicsPredictor.forward")
+        ctx.graph, ctx.A, ctx.S = graph, int(a.shape[1]), int(state_t.shape[1])
+        return _hip.gnn_rel_inputs(torch.cat([a, g, state_t], 1), graph.receivers, graph.senders, a.shape[1], g.shape[1])
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from diff_gaussian_rasterization import _hip
+        gr = ctx.graph
+        return None, None, _hip.gnn_rel_inputs_backward(d_out.contiguous(), gr.row_start, gr.rev_ptr, gr.rev_edge, ctx.A, ctx.S), None
+
+
+class _GnnAggregate(torch.autograd.Function):
+    """gsr_gnn_aggregate_res -> (agg, res_a + res_b) with gsr_gnn_aggregate_backward: the pre-activations are recomputed from the saved
+    inputs (rew1 is one tensor for all propagation steps), the sums walk fixed-order lists -- deterministic gradients."""
+
+    @staticmethod
+    def forward(ctx, rew1, a23, res_a, res_b, graph, n_sum):
+        from diff_gaussian_rasterization import _hip
+        ctx.graph, ctx.n_sum = graph, n_sum
+        ctx.save_for_backward(rew1, a23)
+        return _hip.gnn_aggregate(rew1, a23, graph.senders, graph.row_start, n_sum, res=(res_a, res_b))
+
+    @staticmethod
+    def backward(ctx, d_agg, d_base):
+        from diff_gaussian_rasterization import _hip
+        rew1, a23 = ctx.saved_tensors
+        gr = ctx.graph
+        d_agg = torch.zeros((a23.shape[0], rew1.shape[1]), dtype=a23.dtype, device=a23.device) if d_agg is None else d_agg.contiguous()
+        d_rew1, d_a23 = _hip.gnn_aggregate_backward(rew1, a23, gr.senders, gr.receivers, gr.row_start, gr.rev_ptr, gr.rev_edge, d_agg, ctx.n_sum)
+        return d_rew1, d_a23, d_base, d_base, None, None
 
 
 class DynamicsPredictor(nn.Module):
@@ -385,6 +446,40 @@ class DynamicsPredictor(nn.Module):
         ibuf[:, :E].copy_(torch.stack([receivers, senders]))
         graph.replay()
         return out[0][:N].clone(), out[1][:N].clone()
+
+    # ---- the split path under autograd: training on the device (gsdyn.dyn_train)
+    def split_grad_ok(self, a) -> bool:
+        """What ``_split_ok`` asks, apart from the grad condition."""
+        c = self.model_config
+        return (_GNN_SPLIT and a.is_cuda and a.dtype == torch.float32 and c["nf_effect"] % 4 == 0
+                and c["rel_attr_dim"] > 0 and c["rel_group_dim"] > 0 and c["rel_distance_dim"] > 0 and c["state_dim"] in (0, 1, 3))
+
+    def propagate_split_grad(self, state_t, a, g, act, graph: SplitGraph, dummy_last_row: bool = False):
+        """``_propagate_split``'s algebra, differentiable: state_t [N, 3 n_his], a [N, attr_dim], g [N, G], act [N, action_dim] and a
+        ``split_graph`` (receivers ascending) -> (predicted positions, motions) of all N rows.  The two kernels are autograd nodes whose
+        backward are kernels as well (gsr_gnn_aggregate_backward, gsr_gnn_rel_inputs_backward: fixed-order sums, no atomics -- the
+        gradients are bit-identical from run to run, which the eager path's scatter_add / index_add backward is not); everything else
+        is plain torch.  Gradients reach the parameters, ``state_t`` and ``act``; ``a`` and ``g`` must not require one."""
+        if not self.split_grad_ok(a):
+            raise RuntimeError("propagate_split_grad: float32 on a HIP device with a configuration the split path accepts, please "
+                               "(DynamicsPredictor.forward is the fallback)")
+        c = self.model_config
+        H, N = c["nf_effect"], int(a.shape[0])
+        rel_in = _GnnRelInputs.apply(a, g, state_t, graph)
+        pe = self.particle_encoder(self._particle_inputs(state_t, a, act))
+        re = self.relation_encoder(rel_in)
+        Wr, Wp = self.relation_propagator.linear.weight, self.particle_propagator.linear.weight       # [H, 3H], [H, 2H]
+        w23 = torch.cat([Wr[:, H:2 * H].t(), Wr[:, 2 * H:].t()], 1)
+        rew1 = torch.addmm(self.relation_propagator.linear.bias, re, Wr[:, :H].t())
+        pewp = torch.addmm(self.particle_propagator.linear.bias, pe, Wp[:, :H].t())
+        wp2t = Wp[:, H:].t()
+        effect = pe
+        for _ in range(c["pstep"]):
+            a23 = torch.mm(effect, w23)
+            agg, base = _GnnAggregate.apply(rew1, a23, pewp, effect, graph, N - 1 if dummy_last_row else N)
+            effect = torch.relu(torch.addmm(base, agg, wp2t))
+        pred_motion = self.non_rigid_predictor(effect)
+        return state_t[:, -3:] + torch.clamp(pred_motion, -self.motion_clamp, self.motion_clamp), pred_motion
 
 
 # ------------------------------------------------------------------------------------------ rotations

@@ -528,6 +528,25 @@ int gsr_gnn_aggregate(int32_t n_rows, int32_t n_sum_rows, int32_t width, const f
  * propagator's addend of the step (particle_encode @ Wp1^T + b, plus the effect as the residual) -- one launch less per propagation step. */
 int gsr_gnn_aggregate_res(int32_t n_rows, int32_t n_sum_rows, int32_t width, const float* rel_part, const float* node_parts, const int64_t* senders,
                           const int64_t* row_start, float* agg, const float* res_a, const float* res_b, float* res_out, void* stream);
+/* ---- the backward of the two (gsr_gnn_bwd.hip; gsdyn.dynamics_loss trains the network through them).  Additive to ABI 125.
+ * Next to the receiver segments (row_start) both take the SENDER-side reverse list: rev_edge [n_rel] = the relation ids stably sorted by
+ * sender (ids ascend within a sender), rev_ptr [n_rows + 1] its segment bounds.  No atomics: every output element is one running fp32 sum
+ * in a stated order, bit-identical from run to run.
+ * gsr_gnn_aggregate_backward: z[e] = (rel_part[e] + node_parts[recv_e][0 : width]) + node_parts[send_e][width : 2 width] recomputed as the
+ *   forward forms it; m[e] = (z[e] <= 0) ? 0 : d_agg[recv_e] (threshold_backward: z = +-0 blocks, a NaN z passes), and m[e] = 0 for
+ *   receivers >= n_sum_rows.  d_rel_part[e] = m[e] for the relations of rows < n_sum_rows (the rows of the others are NOT written: the
+ *   caller zeroes them); d_node_parts[i][0 : width] = sum of m over i's receiver segment in list order (0 for i >= n_sum_rows);
+ *   d_node_parts[i][width : 2 width] = sum of m over i's reverse list in ascending e.  The gradients of gsr_gnn_aggregate_res's res_a and
+ *   res_b are the incoming gradient of res_out itself: no call.
+ * gsr_gnn_rel_inputs_backward: d_out [n_rel, 2 attr_dim + 1 + state_cols] -> d_state [n_rows, state_cols],
+ *   d_state[i][s] = (sum over i's receiver segment, list order, of d_out[e][2 attr_dim + 1 + s]) - (sum over i's reverse list, ascending
+ *   e, of the same): two fp32 sums, one subtraction.  The attribute and instance columns get no gradient (constants of the dataset).
+ *   state_cols = 0 and n_rel = 0 are the caller's to serve (-2 here). */
+int gsr_gnn_aggregate_backward(int32_t n_rows, int32_t n_sum_rows, int32_t width, const float* rel_part, const float* node_parts, const int64_t* senders,
+                               const int64_t* receivers, const int64_t* row_start, const int64_t* rev_ptr, const int64_t* rev_edge, const float* d_agg,
+                               float* d_rel_part, float* d_node_parts, void* stream);
+int gsr_gnn_rel_inputs_backward(int32_t n_rows, int32_t attr_dim, int32_t state_cols, const float* d_out, const int64_t* row_start, const int64_t* rev_ptr,
+                                const int64_t* rev_edge, float* d_state, void* stream);
 /* ---- the planner's rollout (gsdyn/plan.py; /root/reference/src/real_world/plan.py:24-154): B action samples advance B copies of one particle
  * state through the propagation network in ONE batch.  Sample b owns the global rows b R .. b R + R - 1 (R = n_obj + 1: the object
  * particles, then the one tool particle at b R + n_obj); row B R is a dummy row behind the last sample that collects the padding.  To
