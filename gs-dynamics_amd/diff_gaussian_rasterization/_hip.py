@@ -95,7 +95,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_construct_edges_rows", "gsr_rollout_step_head", "gsr_rollout_step_motion", "gsr_gnn_aggregate_res", "gsr_arm_depth_cuts",
            "gsr_camera_scratch_bytes", "gsr_sh_backward_views",
            "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update",
-           "gsr_knn_scratch_bytes", "gsr_knn",
+           "gsr_plan_cost_grad", "gsr_knn_scratch_bytes", "gsr_knn",
            "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views",
            "gsr_gnn_aggregate_backward", "gsr_gnn_rel_inputs_backward")
 
@@ -233,6 +233,8 @@ def load_library():
     lib.gsr_plan_step_tail.argtypes = [i32] * 6 + [C.c_float] + [vp] * 7
     lib.gsr_plan_cost.restype = C.c_int
     lib.gsr_plan_cost.argtypes = [i32] * 4 + [vp] * 5 + [C.c_float] * 3 + [vp] * 5
+    lib.gsr_plan_cost_grad.restype = C.c_int
+    lib.gsr_plan_cost_grad.argtypes = [i32] * 4 + [vp] * 5 + [C.c_float] * 3 + [vp] * 7
     lib.gsr_plan_mppi_update.restype = C.c_int
     lib.gsr_plan_mppi_update.argtypes = [i32, i32, vp, vp, C.c_float, C.c_float] + [vp] * 6
     lib.gsr_knn_scratch_bytes.restype = sz; lib.gsr_knn_scratch_bytes.argtypes = [i32]
@@ -1257,6 +1259,30 @@ def plan_cost(state_seqs, actions, state_cur, target, box, pusher_size: float = 
                                  float(pusher_size), float(sharpness), float(penalty_weight), _ptr(reward), _ptr(chamfer), _ptr(coll), _ptr(boxp),
                                  _stream(dev)), "gsr_plan_cost")
     return reward, chamfer, coll, boxp
+
+
+def plan_cost_grad(state_seqs, actions, state_cur, target, box, pusher_size: float = 0.01, sharpness: float = 100.0, penalty_weight: float = 5.0):
+    """gsr_plan_cost_grad (include/gsr.h): ``plan_cost``'s arguments -> (reward [B], chamfer [B], collision [B, T], box_pen [B, T] -- the bits of
+    ``plan_cost`` --, g_state [B, T, n_obj, 3] = d reward_b / d state_seqs[b], g_actions [B, T, 4] = d reward_b / d actions[b]), one launch,
+    no host read."""
+    lib = load_library()
+    _require_device(state_seqs)
+    dev = state_seqs.device
+    for t in (state_seqs, actions, state_cur, target, box):
+        if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev):
+            raise ValueError("plan_cost_grad: contiguous float32 tensors on one device, please")
+    if state_seqs.dim() != 4 or state_seqs.shape[3] != 3:
+        raise ValueError("plan_cost_grad: state_seqs must be [B, T, n_obj, 3]")
+    B, T, n_obj = int(state_seqs.shape[0]), int(state_seqs.shape[1]), int(state_seqs.shape[2])
+    if (tuple(actions.shape) != (B, T, 4) or tuple(state_cur.shape) != (n_obj, 3) or target.dim() != 2 or target.shape[1] != 3 or int(box.numel()) != 4):
+        raise ValueError("plan_cost_grad: shapes do not fit state_seqs [B, T, n_obj, 3] (actions [B, T, 4], state_cur [n_obj, 3], target [M, 3], box [4])")
+    with _on(dev):
+        e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)  # noqa: E731
+        reward, chamfer, coll, boxp, g_state, g_act = e(B), e(B), e(B, T), e(B, T), e(B, T, n_obj, 3), e(B, T, 4)
+        _check(lib.gsr_plan_cost_grad(B, T, n_obj, int(target.shape[0]), _ptr(state_seqs), _ptr(actions), _ptr(state_cur), _ptr(target), _ptr(box),
+                                      float(pusher_size), float(sharpness), float(penalty_weight), _ptr(reward), _ptr(chamfer), _ptr(coll),
+                                      _ptr(boxp), _ptr(g_state), _ptr(g_act), _stream(dev)), "gsr_plan_cost_grad")
+    return reward, chamfer, coll, boxp, g_state, g_act
 
 
 def plan_mppi_update(act_seqs, rewards, reward_weight: float, push_length: float, lower, upper):

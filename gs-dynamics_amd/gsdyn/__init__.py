@@ -9,7 +9,7 @@ from .camera import setup_camera, look_at_w2c, Rt_to_w2c  # noqa: F401
 from .scene import synth_scene_params, synth_ring_cameras, synth_targets  # noqa: F401
 from .step import params2rendervar, get_loss, get_loss_views, loss_and_grads_views, LossWeights, initialize_optimizer  # noqa: F401
 from .plan import (decode_action, rollout_actions, running_cost, mppi_update, sample_action_seq, clip_actions,  # noqa: F401
-                   plan_actions)
+                   plan_actions, running_cost_grad, rollout_actions_grad, plan_actions_gd)
 from .knn import knn_points  # noqa: F401
 from .observe import voxel_down_sample, depth_to_cloud, observe_state  # noqa: F401
 from .dyn_train import dynamics_loss, train_dynamics_step  # noqa: F401

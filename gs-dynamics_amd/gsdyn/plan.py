@@ -26,6 +26,11 @@ target cloud, a collision term at every push's start point, a box term) and ``mp
 are one launch each on a HIP device -- gsr_plan_cost, gsr_plan_mppi_update (csrc/gsr_plan_cost.hip) -- and plain torch elsewhere;
 ``sample_action_seq`` / ``clip_actions`` restate the reference's sampler; ``plan_actions`` is the whole planning step: per chunk and
 iteration sample -> ``rollout_actions`` -> ``running_cost`` -> ``mppi_update``, the best chunk wins.
+
+The gradient planner (the reference's planner type 'GD'; the last section of this file): ``rollout_actions_grad`` is the rollout with an
+autograd graph to the pushes and the model's parameters, ``running_cost_grad`` the cost with a DEFINED gradient -- on a HIP device values and
+gradients in one launch, gsr_plan_cost_grad (csrc/gsr_plan_cost_grad.hip) --, ``plan_actions_gd`` the loop: Adam on the candidates, clip,
+the best candidate seen.
 """
 from __future__ import annotations
 
@@ -74,10 +79,12 @@ def _sample_constants(model: DynamicsPredictor, n_obj: int, dev, dtype):
 
 
 def _rollout_reference(model: DynamicsPredictor, state: torch.Tensor, decoded: torch.Tensor, repeat_host: List[List[int]], adj_thresh: float,
-                       topk: int, n_his: int, trace: list = None) -> torch.Tensor:
+                       topk: int, n_his: int, trace: list = None, detach_steps: bool = False) -> torch.Tensor:
     """The semantic definition: one sample at a time, ``construct_edges`` + ``model._propagate`` per model call.  A sample runs exactly its
     own ``repeat`` calls per look-ahead step (the calls the reference makes beyond that are discarded by it).  ``trace``: a list that
-    receives (sample, li, ai, newest positions [R, 3], receivers, senders) per model call."""
+    receives (sample, li, ai, newest positions [R, 3], receivers, senders) per model call.  Run under ``enable_grad`` it is also the
+    definition of the differentiable rollout (``rollout_actions_grad``); ``detach_steps`` then starts look-ahead step li from the DETACHED
+    state of li - 1, the reference's rule (values unchanged)."""
     B, T, n_obj = decoded.shape[0], decoded.shape[1], state.shape[0]
     dev, dtype = state.device, state.dtype
     a, g, mask, tool = _sample_constants(model, n_obj, dev, dtype)
@@ -105,7 +112,7 @@ def _rollout_reference(model: DynamicsPredictor, state: torch.Tensor, decoded: t
                 hist = torch.cat([hist[1:], pred[None]], 0)
                 eef = torch.cat([eef[1:], eef_new[None]], 0)
             out[b, li] = pred
-            prev = pred
+            prev = pred.detach() if detach_steps else pred
     return out
 
 
@@ -380,3 +387,322 @@ def plan_actions(model: DynamicsPredictor, state: torch.Tensor, target: torch.Te
     chunk_rewards = torch.stack(rewards)
     win = int(torch.argmax(chunk_rewards))                  # the one host read of the cost / update side: which chunk won
     return {"act_seq": seqs[win], "reward": chunk_rewards[win], "state_seqs": states[win], "chunk_rewards": chunk_rewards}
+
+
+# ------------------------------------------------------------------------------------------ the gradient planner
+# The reference's planner has a 'GD' type (utils/planner.py ``trajectory_optimization_gd``: Adam on the sampled pushes, loss = -mean reward).
+# Its own model function is decorated ``no_grad`` and detaches the state between look-ahead steps, so it cannot be run against it; the
+# differentiable rollout is therefore defined HERE: ``_rollout_reference`` under autograd (``detach_steps=True`` is the reference's detach).
+def _first_arg(v: torch.Tensor, dim: int, largest: bool = False) -> torch.Tensor:
+    """The LOWEST index along ``dim`` that attains the minimum (maximum), a NaN counting as the extreme (torch.min / torch.max keep it):
+    ``torch.argmax`` of a mask returns the first."""
+    nan = torch.isnan(v)
+    ext = (v.max(dim=dim, keepdim=True) if largest else v.min(dim=dim, keepdim=True)).values
+    hit = torch.where(nan.any(dim=dim, keepdim=True), nan, v == ext)
+    return hit.to(torch.uint8).argmax(dim=dim)
+
+
+def _root0(d2: torch.Tensor) -> torch.Tensor:
+    """sqrt whose gradient at zero is zero (the subgradient torch.norm uses) instead of inf; a NaN stays."""
+    zero = d2 == 0
+    return torch.where(zero, torch.zeros((), dtype=d2.dtype, device=d2.device), torch.sqrt(torch.where(zero, torch.ones((), dtype=d2.dtype, device=d2.device), d2)))
+
+
+def _gate(x: torch.Tensor) -> torch.Tensor:
+    """max(x, 0) that keeps a NaN and is open iff x > 0 (torch.maximum splits the gradient at x = 0)."""
+    return torch.where(x <= 0, torch.zeros((), dtype=x.dtype, device=x.device), x)
+
+
+class _PoisonRows(torch.autograd.Function):
+    """reward -> reward; toward ``state_seqs`` and ``actions`` it sends NaN into every row of a sample whose reward is not finite (and +0 into
+    the others): the definition's rule for diverged samples, which plain autograd would spread over some rows only."""
+
+    @staticmethod
+    def forward(ctx, reward, state_seqs, actions):
+        ctx.save_for_backward(reward)
+        ctx.shapes = (state_seqs.shape, actions.shape)
+        return reward.clone()
+
+    @staticmethod
+    def backward(ctx, d_reward):
+        (reward,) = ctx.saved_tensors
+        bad = ~torch.isfinite(reward)
+        fill = torch.where(bad, torch.full_like(reward, math.nan), torch.zeros_like(reward))
+        s_shape, a_shape = ctx.shapes
+        return d_reward, fill[:, None, None, None].expand(s_shape), fill[:, None, None].expand(a_shape)
+
+
+def _running_cost_grad_reference(state_seqs: torch.Tensor, actions: torch.Tensor, state_cur: torch.Tensor, target: torch.Tensor, box: torch.Tensor,
+                                 pusher_size: float, sharpness: float, penalty_weight: float):
+    """The definition of the cost's gradient (include/gsr.h, gsr_plan_cost_grad) in plain torch, any dtype; the values are
+    ``_running_cost_reference``'s.  Every minimum / maximum is resolved to ONE index -- the lowest among equal values -- under ``no_grad``
+    (the [b, M, n_obj] table in slices of B, as the fallback builds it); the chosen points are gathered and only the O(B (M + n_obj))
+    distances between them go through autograd.  A zero distance has a zero gradient; the collision and box gates are open iff their
+    argument is > 0; a sample whose reward is not finite sends NaN into all its rows."""
+    B, T, n_obj = state_seqs.shape[0], state_seqs.shape[1], state_seqs.shape[2]
+    M = target.shape[0]
+    last = state_seqs[:, T - 1]
+    with torch.no_grad():
+        step = max(1, COST_TABLE_ENTRIES // max(1, M * n_obj))
+        near_p, near_t = [], []
+        for s in range(0, B, step):
+            P = last[s:s + step]
+            d2 = sum((target[None, :, None, c] - P[:, None, :, c]) ** 2 for c in range(3))   # [b, M, n_obj]
+            near_p.append(_first_arg(d2, 2))                                         # [b, M]: target m's nearest particle
+            near_t.append(_first_arg(d2, 1))                                         # [b, n_obj]: particle n's nearest target
+        near_p, near_t = torch.cat(near_p, 0), torch.cat(near_t, 0)
+    Pn = last.gather(1, near_p[:, :, None].expand(-1, -1, 3))                        # [B, M, 3]
+    Qn = target[near_t]                                                              # [B, n_obj, 3]
+    d_a = _root0(sum((target[None, :, c] - Pn[:, :, c]) ** 2 for c in range(3)))
+    d_b = _root0(sum((Qn[:, :, c] - last[:, :, c]) ** 2 for c in range(3)))
+    chamfer = d_a.mean(dim=1) + d_b.mean(dim=1)
+    frames = torch.cat([state_cur[None, None, :, :2].expand(B, 1, n_obj, 2), state_seqs[:, :T - 1, :, :2]], 1)   # [B, T, n_obj, 2]
+    with torch.no_grad():
+        hit = _first_arg(((actions[:, :, None, :2] - frames) ** 2).sum(-1), 2)       # [B, T]
+    q = frames.gather(2, hit[:, :, None, None].expand(-1, -1, 1, 2))[:, :, 0]        # [B, T, 2]
+    collision = torch.exp(-sharpness * _gate(_root0(((actions[:, :, :2] - q) ** 2).sum(-1)) - pusher_size))
+    x, y = state_seqs[..., 0], state_seqs[..., 1]                                    # [B, T, n_obj]
+    with torch.no_grad():
+        ix = [_first_arg(x, 2), _first_arg(x, 2, largest=True), _first_arg(y, 2), _first_arg(y, 2, largest=True)]
+    pick = lambda v, i: v.gather(2, i[:, :, None])[:, :, 0]  # noqa: E731
+    margins = torch.stack([pick(x, ix[0]) - box[0], box[1] - pick(x, ix[1]), pick(y, ix[2]) - box[2], box[3] - pick(y, ix[3])], -1)
+    e = torch.exp(-sharpness * _gate(margins))                                       # [B, T, 4]
+    with torch.no_grad():
+        wall = _first_arg(e, 2, largest=True)
+    box_pen = e.gather(2, wall[:, :, None])[:, :, 0]
+    reward = -chamfer - penalty_weight * collision.mean(dim=1) - penalty_weight * box_pen.mean(dim=1)
+    if state_seqs.requires_grad or actions.requires_grad:
+        reward = _PoisonRows.apply(reward, state_seqs, actions)
+    return reward, chamfer.detach(), collision.detach(), box_pen.detach()
+
+
+class _PlanCostGrad(torch.autograd.Function):
+    """gsr_plan_cost_grad: the four values and, saved for the backward, the per-sample gradients; the backward scales row b by d_reward[b]."""
+
+    @staticmethod
+    def forward(ctx, state_seqs, actions, state_cur, target, box, pusher_size, sharpness, penalty_weight):
+        from diff_gaussian_rasterization import _hip
+        r, ch, co, bp, g_state, g_act = _hip.plan_cost_grad(state_seqs.contiguous(), actions.contiguous(), state_cur.contiguous(), target.contiguous(),
+                                                            box.contiguous(), pusher_size, sharpness, penalty_weight)
+        ctx.save_for_backward(g_state, g_act)
+        ctx.mark_non_differentiable(ch, co, bp)
+        return r, ch, co, bp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_reward, *_):
+        g_state, g_act = ctx.saved_tensors
+        return g_state * d_reward[:, None, None, None], g_act * d_reward[:, None, None], None, None, None, None, None, None
+
+
+def running_cost_grad(state_seqs: torch.Tensor, actions: torch.Tensor, state_cur: torch.Tensor, target: torch.Tensor, bbox, *, pusher_size: float = 0.01,
+                      sharpness: float = 100.0, penalty_weight: float = 5.0) -> Dict[str, torch.Tensor]:
+    """``running_cost`` with a gradient: the same dictionary, the same values; "reward_seqs" carries an autograd graph to ``state_seqs`` and
+    ``actions`` (columns 0, 1; columns 2, 3 receive zeros from the cost -- their gradient comes through the rollout), the other three
+    entries are detached.  The gradient is DEFINED (include/gsr.h, gsr_plan_cost_grad; ``_running_cost_grad_reference`` states it in torch):
+    every minimum and maximum hands its gradient to the lowest index among equal values, a zero distance contributes a zero vector and
+    never a NaN, the collision and box gates are open iff their argument is > 0, and a sample whose reward is not finite gets NaN in all
+    its rows.  float32 tensors on a HIP device with at most 1024 particles take gsr_plan_cost_grad -- values and gradients in one launch,
+    no [B, M, n_obj] table, once differentiable, bit-identical from run to run; everything else (CPU tensors, other dtypes, a ``state_cur``,
+    ``target`` or ``bbox`` that requires a gradient) takes the torch statement."""
+    if (state_seqs.dim() != 4 or state_seqs.shape[3] != 3 or actions.dim() != 3 or actions.shape[2] != 4 or actions.shape[:2] != state_seqs.shape[:2]
+            or tuple(state_cur.shape) != (state_seqs.shape[2], 3) or target.dim() != 2 or target.shape[1] != 3):
+        raise ValueError("running_cost_grad: state_seqs [B, T, n_obj, 3], actions [B, T, 4], state_cur [n_obj, 3] and target [M, 3], please")
+    if min(state_seqs.shape[0], state_seqs.shape[1], state_seqs.shape[2], target.shape[0]) < 1:
+        raise ValueError("running_cost_grad: B, T, n_obj and M must be at least 1")
+    box = _box4(bbox, state_seqs.device, state_seqs.dtype)
+    side_grad = state_cur.requires_grad or target.requires_grad or box.requires_grad
+    if _cost_device_ok(state_seqs, actions, state_cur, target) and int(state_seqs.shape[2]) <= MAX_COST_PARTICLES and not side_grad:
+        r, ch, co, bp = _PlanCostGrad.apply(state_seqs, actions, state_cur, target, box, pusher_size, sharpness, penalty_weight)
+    else:
+        r, ch, co, bp = _running_cost_grad_reference(state_seqs, actions, state_cur, target.to(state_seqs.dtype), box, pusher_size, sharpness,
+                                                     penalty_weight)
+    return {"reward_seqs": r, "chamfer": ch, "collision": co, "box": bp}
+
+
+def _batched_call_grad(model: DynamicsPredictor, states: List[torch.Tensor], delta: torch.Tensor, a: torch.Tensor, g: torch.Tensor,
+                       n_valid: torch.Tensor, adj_thresh: float, topk: int, e_cap: int):
+    """ONE differentiable model call for all samples: states = n_his frames [B, R, 3] (each sample's tool row last), delta [B, 3] the tool's
+    motion, a / g the constant rows [B R + 1, .] -> (predicted positions [B, R, 3], (receivers, senders, count, row_start)).  The B graphs
+    are one block-diagonal graph (sample b owns the rows b R .. b R + R - 1, one zero dummy row last collects the padded relations); the
+    relations come from gsr_construct_edges_batch on the DETACHED newest frame -- relations are discrete -- and the network is
+    ``propagate_split_grad``.  The sender-side reverse list is built with a stable sort and a search: no host read."""
+    from diff_gaussian_rasterization import _hip
+    from .dynamics import SplitGraph
+    B, R, dev = int(delta.shape[0]), int(states[0].shape[1]), delta.device
+    N = B * R + 1
+    state_t = torch.cat([torch.cat(states, 2).reshape(B * R, 3 * len(states)), torch.zeros((1, 3 * len(states)), device=dev)], 0)
+    act = torch.cat([torch.cat([torch.zeros((B, R - 1, 3), device=dev), delta[:, None]], 1).reshape(B * R, 3), torch.zeros((1, 3), device=dev)], 0)
+    recv, send, cnt, rows = _hip.construct_edges_batch(states[-1].detach().contiguous(), n_valid, adj_thresh, topk, e_cap)
+    order = torch.argsort(send, stable=True)
+    rev_ptr = torch.searchsorted(send[order].contiguous(), torch.arange(N + 1, device=dev, dtype=torch.int64))
+    graph = SplitGraph(recv, send, rows, rev_ptr, order.contiguous())
+    pos, _ = model.propagate_split_grad(state_t, a, g, act, graph, dummy_last_row=True)
+    return pos[:B * R].view(B, R, 3), (recv, send, cnt, rows)
+
+
+def _batched_constants(model: DynamicsPredictor, B: int, n_obj: int, topk: int, dev):
+    """The constant rows of B samples and the dummy row, the valid count and the relation capacity of ``_batched_call_grad``."""
+    from diff_gaussian_rasterization import _hip
+    a1, g1, _, _ = _sample_constants(model, n_obj, dev, torch.float32)
+    a = torch.cat([a1.repeat(B, 1), torch.zeros((1, a1.shape[1]), device=dev)], 0).contiguous()
+    g = torch.cat([g1.repeat(B, 1), torch.zeros((1, 1), device=dev)], 0).contiguous()
+    return a, g, torch.full((1,), n_obj, dtype=torch.int32, device=dev), _hip.plan_edge_capacity(B, n_obj, topk)
+
+
+def _rollout_device_grad(model: DynamicsPredictor, state: torch.Tensor, decoded: torch.Tensor, repeat: torch.Tensor, max_repeat: List[int],
+                         adj_thresh: float, topk: int, n_his: int, detach_steps: bool, trace: list = None) -> torch.Tensor:
+    """``_rollout_device``'s structure with the glue as differentiable torch operations around ``_batched_call_grad``.  No host read inside
+    the loops.  ``trace``: receives (li, ai, newest frame [B, R, 3], receivers, senders, count) per model call."""
+    B, T, n_obj = int(decoded.shape[0]), int(decoded.shape[1]), int(state.shape[0])
+    dev = state.device
+    a, g, n_valid, e_cap = _batched_constants(model, B, n_obj, topk, dev)
+    zero_col = torch.zeros((B, 1), device=dev)
+    outs, prev = [], state[None].expand(B, -1, -1)
+    for li in range(T):
+        hist = [prev] * n_his                                                        # each [B, n_obj, 3]
+        eef = [torch.cat([decoded[:, li, :2], prev[:, :, 2].min(dim=1).values[:, None]], 1)] * n_his      # each [B, 3]
+        delta = torch.cat([decoded[:, li, 2:4] - decoded[:, li, 0:2], zero_col], 1)  # [B, 3]
+        out_li = torch.zeros((B, n_obj, 3), device=dev)
+        for ai in range(1, max_repeat[li] + 1):
+            states = [torch.cat([h, e[:, None]], 1) for h, e in zip(hist, eef)]      # n_his x [B, R, 3], the tool last
+            pos, (recv, send, cnt, _) = _batched_call_grad(model, states, delta, a, g, n_valid, adj_thresh, topk, e_cap)
+            if trace is not None:
+                trace.append((li, ai, states[-1].detach().clone(), recv, send, cnt))
+            pred = pos[:, :n_obj]
+            out_li = torch.where((repeat[:, li] == ai)[:, None, None], pred, out_li)
+            hist = hist[1:] + [pred]
+            eef = eef[1:] + [torch.cat([eef[-1][:, :2] + delta[:, :2], pred[:, :, 2].min(dim=1).values[:, None]], 1)]
+        outs.append(out_li)
+        prev = out_li.detach() if detach_steps else out_li
+    return torch.stack(outs, 1)
+
+
+def _grad_device_path_ok(model: DynamicsPredictor, probe: torch.Tensor, n_obj: int) -> bool:
+    """``_device_path_ok`` for the differentiable rollout: ``split_grad_ok`` in place of the inference condition."""
+    c = model.model_config
+    return bool(model.split_grad_ok(probe) and model.motion_dim == 0 and c["state_dim"] in (0, 3) and c["action_dim"] == 3 and c["attr_dim"] >= 2
+                and 1 <= int(n_obj) <= MAX_DEVICE_PARTICLES)
+
+
+def rollout_actions_grad(model: DynamicsPredictor, state: torch.Tensor, actions: torch.Tensor, *, push_length: float, adj_thresh: float, topk: int = 5,
+                         n_his: int = 3, detach_steps: bool = False, device_path: Optional[bool] = None, _trace: list = None) -> Dict[str, torch.Tensor]:
+    """``rollout_actions`` with a gradient: state [n_obj, 3], actions [B, T, 4] -> {"state_seqs": [B, T, n_obj, 3], "action_seqs": [B, T, 4]}
+    with an autograd graph to ``actions`` (columns 0 - 2; ``repeat = int(length)`` has none) and to the model's parameters.  The DEFINITION
+    is ``_rollout_reference`` run under ``enable_grad``: the reference's own model function is ``no_grad`` and detaches the state between
+    look-ahead steps, so its GD planner cannot run against it -- a departure by necessity.  ``detach_steps=True`` is the reference's rule:
+    look-ahead step li starts from the detached state of li - 1 (values unchanged).  The relations are discrete: they are built from the
+    detached newest positions; the tool's z follows the lowest particle through its arg-min.  No chunking: the caller chunks (activations
+    grow with B times the sum of the repeat counts).
+    ``device_path``: None -- the batched device path (``_rollout_device_grad``: one ``propagate_split_grad`` call for all samples per model
+    call, no host read inside the loops) wherever it can run: float32 on a HIP device, a model the split path accepts, at most 127
+    particles; the definition everywhere else.  True asks for the device path and raises where it cannot run; False is the definition."""
+    if state.dim() != 2 or state.shape[1] != 3 or actions.dim() != 3 or actions.shape[2] != 4:
+        raise ValueError("rollout_actions_grad: state [n_obj, 3] and actions [B, T, 4], please")
+    if int(model.model_config["n_his"]) != int(n_his):
+        raise ValueError(f"rollout_actions_grad: n_his = {n_his}, the model was built for {model.model_config['n_his']}")
+    if actions.device != state.device:
+        raise ValueError("rollout_actions_grad: state and actions on one device, please")
+    B, T, n_obj = int(actions.shape[0]), int(actions.shape[1]), int(state.shape[0])
+    with torch.enable_grad():
+        decoded, repeat = decode_action(actions, push_length)
+        if B == 0 or T == 0:
+            return {"state_seqs": torch.zeros((B, T, n_obj, 3), dtype=state.dtype, device=state.device), "action_seqs": decoded}
+        can = _grad_device_path_ok(model, state, n_obj) and decoded.dtype == torch.float32
+        if device_path and not can:
+            raise RuntimeError("rollout_actions_grad: the device path needs float32 on a HIP device, a model the split path accepts and at most "
+                               f"{MAX_DEVICE_PARTICLES} particles")
+        use_device = can if device_path is None else bool(device_path)
+        if use_device:
+            stats = torch.cat([repeat.amin().view(1), repeat.amax(0)]).cpu().tolist()    # the ONE host read: the loop bounds
+            lo, maxes = stats[0], stats[1:]
+        else:
+            repeat_host = repeat.cpu().tolist()
+            lo = min(min(r) for r in repeat_host)
+        if lo < 1:
+            raise ValueError(f"rollout_actions_grad: every action must repeat at least once (int(length) >= 1), found {lo}")
+        if use_device:
+            out = _rollout_device_grad(model, state.contiguous(), decoded, repeat, maxes, adj_thresh, topk, n_his, detach_steps, _trace)
+        else:
+            out = _rollout_reference(model, state, decoded, repeat_host, adj_thresh, topk, n_his, _trace, detach_steps=detach_steps)
+    return {"state_seqs": out, "action_seqs": decoded}
+
+
+def _best_index(rewards: torch.Tensor) -> torch.Tensor:
+    """The lowest b that attains the largest reward, a NaN counting as the largest -- ``mppi_update``'s ranking; no host read."""
+    return _first_arg(rewards, 0, largest=True)
+
+
+def plan_actions_gd(model: DynamicsPredictor, state: torch.Tensor, target: torch.Tensor, bbox, act_seq: torch.Tensor, *, lower, upper, push_length: float,
+                    adj_thresh: float, n_sample: int = 32, n_update_iter: int = 10, lr: float = 1e-3, init: Optional[torch.Tensor] = None, topk: int = 5,
+                    n_his: int = 3, detach_steps: bool = False, rollout_best: bool = True,
+                    generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+    """The reference's ``trajectory_optimization_gd`` (utils/planner.py, planner type 'GD') for one chunk: Adam on B candidate push sequences
+    with loss = -sum(reward) / B, ``clip_actions`` after every step, the best candidate returned.  state [n_obj, 3], target [M, 3], bbox as
+    ``running_cost`` takes it, act_seq [T, 4] -> {"act_seq" [T, 4], "reward" (scalar), "state_seqs" [T, n_obj, 3], "reward_history"
+    [n_update_iter]: the best reward seen up to each iteration}.
+    The candidates are ``init`` ([B, T, 4] -- for instance MPPI's best samples, to refine them) or ``sample_action_seq(act_seq, ...,
+    iter_index=0)`` with ``n_sample`` rows.  Per iteration: ``rollout_actions_grad`` -> ``running_cost_grad`` -> the gradient toward the
+    candidates only (the model's parameters accumulate nothing) -> non-finite gradient rows set to zero on the device -> Adam(lr, betas =
+    (0.9, 0.999)) -> ``clip_actions``.  The length column receives a zero gradient (``repeat = int(length)``) and Adam leaves it where it is.
+    Two stated departures from the reference.  It keeps the best (sample, reward, rollout) seen AT EVALUATION TIME, ranked as
+    ``plan_actions`` ranks (the lowest index among equals, a NaN as the largest); the reference indexes the stepped actions with the
+    pre-step rewards.  And the differentiable rollout is defined here (``rollout_actions_grad``); ``detach_steps=True`` is the reference's
+    detach between look-ahead steps.  The last iteration's step could never be evaluated and is not taken.
+    ``rollout_best`` as in ``plan_actions``.  Host reads: the one ``rollout_actions_grad`` makes per call for its loop bounds; the ranking and
+    the gradient clean-up make none.  Nothing is printed."""
+    if act_seq.dim() != 2 or act_seq.shape[1] != 4:
+        raise ValueError("plan_actions_gd: act_seq [T, 4] = (x, y, theta, length), please")
+    if int(n_update_iter) < 1:
+        raise ValueError("plan_actions_gd: n_update_iter must be at least 1")
+    dev, dtype = state.device, state.dtype
+    lower = torch.as_tensor(lower, dtype=dtype, device=dev)
+    upper = torch.as_tensor(upper, dtype=dtype, device=dev)
+    act_seq = act_seq.to(device=dev, dtype=dtype)
+    target = target.to(device=dev, dtype=dtype)
+    bbox = torch.as_tensor(bbox)[:2, :2].to(device=dev, dtype=dtype)
+    if init is not None:
+        if init.dim() != 3 or init.shape[1:] != act_seq.shape or init.shape[0] < 1:
+            raise ValueError("plan_actions_gd: init [B, T, 4] with act_seq's T, please")
+        acts = init.detach().to(device=dev, dtype=dtype).clone()
+    else:
+        if int(n_sample) < 1:
+            raise ValueError("plan_actions_gd: n_sample must be at least 1")
+        acts = sample_action_seq(act_seq, lower, upper, int(n_sample), iter_index=0, noise_level=1.0, push_length=push_length, generator=generator)
+    acts = acts.contiguous().requires_grad_(True)
+    B = int(acts.shape[0])
+    opt = torch.optim.Adam([acts], lr=lr, betas=(0.9, 0.999))
+    roll = dict(push_length=push_length, adj_thresh=adj_thresh, topk=topk, n_his=n_his)
+    best, history = None, []
+    for it in range(int(n_update_iter)):
+        final = it == int(n_update_iter) - 1
+        with torch.set_grad_enabled(not final):
+            out = rollout_actions_grad(model, state, acts, detach_steps=detach_steps, **roll)["state_seqs"] if not final else \
+                rollout_actions(model, state, acts.detach(), chunk=B, **roll)["state_seqs"]
+            cost = running_cost_grad(out, acts, state, target, bbox) if not final else running_cost(out, acts.detach(), state, target, bbox)
+        rewards = cost["reward_seqs"]
+        with torch.no_grad():
+            idx = _best_index(rewards.detach()).view(1)
+            cand = (acts.detach().index_select(0, idx)[0].clone(), rewards.detach().index_select(0, idx)[0], out.detach().index_select(0, idx)[0])
+            if best is None:
+                best = cand
+            else:
+                take = cand[1] > best[1]
+                best = tuple(torch.where(take, c, o) for c, o in zip(cand, best))
+            history.append(best[1])
+        if final:
+            break
+        (grad,) = torch.autograd.grad(-rewards.sum() / B, acts)
+        with torch.no_grad():
+            ok = torch.isfinite(grad).all(dim=2).all(dim=1)[:, None, None]
+            acts.grad = torch.where(ok, grad, torch.zeros_like(grad))
+        opt.step()
+        with torch.no_grad():
+            acts.data.copy_(clip_actions(acts.data, lower, upper))
+    seq, reward, st = best
+    if rollout_best:
+        with torch.no_grad():
+            st = rollout_actions(model, state, seq[None], chunk=1, **roll)["state_seqs"]
+            reward = running_cost(st, seq[None], state, target, bbox)["reward_seqs"][0]
+            st = st[0]
+    return {"act_seq": seq, "reward": reward, "state_seqs": st, "reward_history": torch.stack(history)}

@@ -599,6 +599,31 @@ int gsr_plan_cost(int32_t B, int32_t T, int32_t n_obj, int32_t M, const float* s
                   float* collision, float* box_pen, void* stream);
 int gsr_plan_mppi_update(int32_t B, int32_t T, const float* act_seqs, const float* rewards, float reward_weight, float push_length, const float* lower,
                          const float* upper, float* act_seq, int64_t* best_index, float* best_reward, void* stream);
+/* ---- the gradient planner's cost (csrc/gsr_plan_cost_grad.hip; gsdyn.running_cost_grad).  Additive to ABI 125.
+ * gsr_plan_cost_grad: gsr_plan_cost's inputs -> its four outputs, BIT-IDENTICAL to gsr_plan_cost's on the same inputs, and in the same launch
+ *   g_state [B, T, n_obj, 3] = d reward[b] / d state_seqs[b] and g_actions [B, T, 4] = d reward[b] / d actions[b].  A sample's reward depends
+ *   on its own rows only: an autograd node scales row b by the incoming d_reward[b].  One rule set (gsdyn.plan._running_cost_grad_reference is
+ *   its statement in torch):
+ *   minima, maxima: each hands its gradient to ONE element, the LOWEST index among equal values; for the chamfer and collision minima the
+ *                   decision is taken on the squared distance, as the forward takes it.
+ *   chamfer (last frame P): particle n receives -(1 / n_obj) (P_n - q_m*(n)) / |.|, m*(n) its nearest target, and for every target m whose
+ *                   nearest particle is n, -(1 / M) (P_n - q_m) / |.|, those summed in ascending m in fp32 from +0 (the unit vectors are
+ *                   summed, the factor comes once behind the sum).  A zero distance contributes a zero vector -- the subgradient torch.norm
+ *                   uses --, never a NaN.
+ *   collision at step t: c = exp(-sharpness max(d - pusher_size, 0)), d the distance from the start point (a_x, a_y) to the nearest xy of the
+ *                   frame the push meets.  The gate is open iff d - pusher_size > 0.  With u the unit vector from that particle to the start
+ *                   point, d reward / d (a_x, a_y) = +(penalty_weight / T) sharpness c u; the xy of that one particle -- in state_seqs[b, t - 1];
+ *                   at t = 0 in state_cur, which receives no gradient -- receives the opposite.
+ *   box at step t:  the active wall is the lowest index among (x_lo, x_hi, y_lo, y_hi) that attains the maximum; a margin <= 0 gives zero;
+ *                   otherwise d reward / d margin = +(penalty_weight / T) sharpness e goes to the x or y of the one particle that attains that
+ *                   wall's extreme (lowest index), with the sign the margin has in that coordinate.
+ *   g_actions' columns 2 and 3 (angle, length) are written as zeros: their gradient comes through the rollout.
+ *   A sample whose reward is not finite gets NaN in ALL its g_state and g_actions rows; other samples are untouched.
+ *   Every output element is written by one thread as a fixed-order fp32 sum; no atomics on global memory: bit-identical from run to run and
+ *   independent of B and of the sample's position in the batch.  Limits and refusals are gsr_plan_cost's (-2 and no launch). */
+int gsr_plan_cost_grad(int32_t B, int32_t T, int32_t n_obj, int32_t M, const float* state_seqs, const float* actions, const float* state_cur,
+                       const float* target, const float* box, float pusher_size, float sharpness, float penalty_weight, float* reward,
+                       float* chamfer, float* collision, float* box_pen, float* g_state, float* g_actions, void* stream);
 /* ---- exact k-nearest-neighbour search (csrc/gsr_knn.hip; gsdyn.knn_points).  Additive to ABI 125.
  * points [N, 3] fp32 on the device -> out_idx [N, k] int64, out_d2 [N, k] fp32.  The distance of query i to point j is
  *   d2 = (dx*dx + dy*dy) + dz*dz,  dx = p[i].x - p[j].x (and so on), every operation fp32, in that order, unfused;
