@@ -76,4 +76,97 @@ __device__ __forceinline__ void gsr_rel_write_row(unsigned long long m0, unsigne
   if ((m1 >> lane) & 1ull) { const int e = base + __popcll(m0) + __popcll(m1 & lt); if (e < e_cap) { recv[e] = row0 + i; send[e] = row0 + lane + 64; } }
 }
 
+// ---------------------------------------------------------------- graphs of up to 256 rows: the training batches (gsr_dyn_batch.hip)
+// Siblings of the three functions above for N = n_obj_cap + 1 <= 256 rows (the cloth configurations have 151): lane l holds the senders
+// l, l + 64, l + 128, l + 192 and a row is FOUR ballot masks.  The rule is the same, with one addition: `connect_all` relates every real
+// object with the tool in both directions whatever the distance (never the tool with itself).  The functions above are untouched, so
+// their users' lists keep their bits.
+__device__ __forceinline__ void gsr_rel4_row_masks(const float* sp, int i, int lane, int N, int n_obj_cap, int n_valid, float thr2, int k,
+                                                   bool connect_all, unsigned long long m[4]) {
+  const bool i_tool = i == n_obj_cap, i_obj = i < n_valid;
+  const float px = sp[3 * i], py = sp[3 * i + 1], pz = sp[3 * i + 2];
+  unsigned long long key[4];
+  bool near_[4];
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const int j = lane + 64 * h;
+    float d = __builtin_inff();
+    if (j < N) {
+      const float dx = px - sp[3 * j], dy = py - sp[3 * j + 1], dz = pz - sp[3 * j + 2];
+      d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    }
+    near_[h] = d < thr2;
+    key[h] = j < n_valid ? (((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j) : ~0ull;   // (d >= 0: its bits order like its value)
+  }
+  unsigned long long kth = 0ull;
+  bool first = true;
+  if (i_obj)
+    for (int q = 0; q < k; ++q) {
+      unsigned long long c = ~0ull;
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const unsigned long long ch = (first || key[h] > kth) ? key[h] : ~0ull;
+        c = ch < c ? ch : c;
+      }
+      kth = gsr_wave_min64(c);
+      first = false;
+    }
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const int j = lane + 64 * h;
+    const bool j_tool = j == n_obj_cap, j_obj = j < n_valid;
+    bool rel;
+    if (i_obj && j_obj) rel = near_[h] && key[h] <= kth;
+    else rel = ((i_obj && j_tool) || (i_tool && j_obj)) && (near_[h] || connect_all);
+    m[h] = __ballot(rel);
+  }
+}
+
+// Exclusive scan of the N <= 256 row counts by ONE wave (four rows per lane): s_base[i] = the list entries before row i, all 256 slots
+// written.  Returns the graph's total, valid in lane 63.
+__device__ __forceinline__ int gsr_rel4_scan_rows(const unsigned long long (*s_mask)[4], int lane, int N, int* s_base) {
+  int c[4], inc[4];
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const int i = lane + 64 * h;
+    c[h] = i < N ? __popcll(s_mask[i][0]) + __popcll(s_mask[i][1]) + __popcll(s_mask[i][2]) + __popcll(s_mask[i][3]) : 0;
+    inc[h] = c[h];
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const int o = __shfl_up(inc[h], d, 64);
+      if (lane >= d) inc[h] += o;
+    }
+  }
+  int before = 0;
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    s_base[lane + 64 * h] = before + inc[h] - c[h];
+    before += __shfl(inc[h], 63, 64);
+  }
+  return before;
+}
+
+// Row i's list entries from its four masks, by one wave, in LOCAL rows: entry base + (the row's set bits below the sender's), dropped at
+// e_cap.  Rr / Rs (both or neither): the one-hot matrices [e_cap, N] of the same list, zeroed by the caller -- only the ones are written.
+__device__ __forceinline__ void gsr_rel4_write_row(const unsigned long long m[4], int i, int lane, int base, int e_cap, int N,
+                                                   long long* __restrict__ recv, long long* __restrict__ send, float* __restrict__ Rr,
+                                                   float* __restrict__ Rs) {
+  const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+  int before = base;
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    if ((m[h] >> lane) & 1ull) {
+      const int e = before + __popcll(m[h] & lt), j = lane + 64 * h;
+      if (e < e_cap) {
+        recv[e] = i; send[e] = j;
+        if (Rr) { Rr[(size_t)e * N + i] = 1.0f; Rs[(size_t)e * N + j] = 1.0f; }
+      }
+    }
+    before += __popcll(m[h]);
+  }
+}
+
 #endif  // __HIPCC__

@@ -97,7 +97,8 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_construct_edges_batch", "gsr_plan_step_head", "gsr_plan_step_tail", "gsr_plan_cost", "gsr_plan_mppi_update",
            "gsr_plan_cost_grad", "gsr_knn_scratch_bytes", "gsr_knn",
            "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views",
-           "gsr_gnn_aggregate_backward", "gsr_gnn_rel_inputs_backward")
+           "gsr_gnn_aggregate_backward", "gsr_gnn_rel_inputs_backward",
+           "gsr_dyn_batch_sample", "gsr_dyn_batch_relations", "gsr_dyn_batch_graph")
 
 
 def load_library():
@@ -246,6 +247,12 @@ def load_library():
     lib.gsr_voxel_points.argtypes = [i32, vp, vp, F3, F3, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.gsr_voxel_depth_views.restype = C.c_int
     lib.gsr_voxel_depth_views.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, F3, F3, C.c_float, C.c_float, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.gsr_dyn_batch_sample.restype = C.c_int
+    lib.gsr_dyn_batch_sample.argtypes = [i32] * 6 + [vp] * 20
+    lib.gsr_dyn_batch_relations.restype = C.c_int
+    lib.gsr_dyn_batch_relations.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.gsr_dyn_batch_graph.restype = C.c_int
+    lib.gsr_dyn_batch_graph.argtypes = [i32, i32, i32] + [vp] * 10
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1194,6 +1201,70 @@ def construct_edges_batch(pos: torch.Tensor, n_valid: torch.Tensor, thresh: floa
         _check(lib.gsr_construct_edges_batch(B, _ptr(p), R - 1, _ptr(n_valid), thr2, int(topk), e_cap, _ptr(recv), _ptr(send), _ptr(cnt), _ptr(rows),
                                              _ptr(scratch), _stream(dev)), "gsr_construct_edges_batch")
     return recv, send, cnt, rows
+
+
+DYN_MAX_P, DYN_MAX_NOBJ, DYN_MAX_TOPK = 1024, 255, 16      # GSR_DYN_MAX_P, GSR_DYN_MAX_NOBJ, GSR_REL_MAXK (include/gsr.h)
+
+
+def dyn_batch_sample(particles, eef, pairs, n_particles, start_idx, thin_start, fps_radius, rot, noise, n_his: int, n_future: int, max_nobj: int):
+    """gsr_dyn_batch_sample (include/gsr.h): contiguous tensors on one HIP device -- particles [F, P, 3] / eef [F, 3] / fps_radius [B] / rot
+    [B, 3, 3] / noise [B, n_his, N, 3] or None fp32, pairs [B, n_his + n_future] int64, n_particles (or None) / start_idx / thin_start [B]
+    int32 -> dict of the sample kernel's outputs.  One launch, no host read."""
+    lib = load_library()
+    _require_device(particles)
+    dev = particles.device
+    F, P = int(particles.shape[0]), int(particles.shape[1])
+    B, N = int(pairs.shape[0]), int(max_nobj) + 1
+    f32 = dict(dtype=torch.float32, device=dev)
+    with _on(dev):
+        out = dict(state=torch.empty((B, n_his, N, 3), **f32), action=torch.empty((B, N, 3), **f32),
+                   tool_future=torch.empty((B, n_future - 1, N, 3), **f32), action_future=torch.empty((B, n_future - 1, N, 3), **f32),
+                   state_future=torch.empty((B, n_future, max_nobj, 3), **f32), attrs=torch.empty((B, N, 2), **f32),
+                   p_instance=torch.empty((B, max_nobj, 1), **f32), obj_mask=torch.empty((B, max_nobj), dtype=torch.bool, device=dev),
+                   n_obj=torch.empty((B,), dtype=torch.int32, device=dev), fps_idx=torch.empty((B, max_nobj), dtype=torch.int64, device=dev))
+        _check(lib.gsr_dyn_batch_sample(B, F, P, int(n_his), int(n_future), int(max_nobj), _ptr(particles), _ptr(eef), _ptr(pairs), _ptr(n_particles),
+                                        _ptr(start_idx), _ptr(thin_start), _ptr(fps_radius), _ptr(rot), _ptr(noise), _ptr(out["state"]),
+                                        _ptr(out["action"]), _ptr(out["tool_future"]) if n_future > 1 else None,
+                                        _ptr(out["action_future"]) if n_future > 1 else None, _ptr(out["state_future"]), _ptr(out["attrs"]),
+                                        _ptr(out["p_instance"]), _ptr(out["obj_mask"]), _ptr(out["n_obj"]), _ptr(out["fps_idx"]), _stream(dev)),
+               "gsr_dyn_batch_sample")
+    return out
+
+
+def dyn_batch_relations(state, n_obj, adj_thresh, topk: int, connect_all: bool, max_nR: int, dense: bool):
+    """gsr_dyn_batch_relations (include/gsr.h): state [B, n_his, N, 3] fp32, n_obj [B] int32, adj_thresh [B] fp32 -> (receivers, senders
+    [B, max_nR] int64 in local rows, padded with N; n_rel [B] int32, the TRUE counts; Rr, Rs [B, max_nR, N] or None, None).  No host read."""
+    lib = load_library()
+    _require_device(state)
+    dev = state.device
+    B, n_his, N = int(state.shape[0]), int(state.shape[1]), int(state.shape[2])
+    with _on(dev):
+        recv = torch.empty((B, max_nR), dtype=torch.int64, device=dev)
+        send = torch.empty((B, max_nR), dtype=torch.int64, device=dev)
+        n_rel = torch.empty((B,), dtype=torch.int32, device=dev)
+        Rr = torch.zeros((B, max_nR, N), dtype=torch.float32, device=dev) if dense else None
+        Rs = torch.zeros((B, max_nR, N), dtype=torch.float32, device=dev) if dense else None
+        _check(lib.gsr_dyn_batch_relations(B, n_his, N - 1, _ptr(state), _ptr(n_obj), _ptr(adj_thresh), int(topk), int(bool(connect_all)), int(max_nR),
+                                           _ptr(recv), _ptr(send), _ptr(n_rel), _ptr(Rr), _ptr(Rs), _stream(dev)), "gsr_dyn_batch_relations")
+    return recv, send, n_rel, Rr, Rs
+
+
+def dyn_batch_graph(recv_pad, send_pad, n_rel, n_rows: int, n_total: int):
+    """gsr_dyn_batch_graph (include/gsr.h): the padded lists [B, max_nR] and their counts n_rel [B] (int32, on the device, each <= max_nR,
+    ``n_total`` their sum as the caller read it) -> (receivers, senders [E], row_start, rev_ptr [B n_rows + 1], rev_edge [E]), int64."""
+    lib = load_library()
+    _require_device(recv_pad)
+    dev = recv_pad.device
+    B, max_nR = int(recv_pad.shape[0]), int(recv_pad.shape[1])
+    with _on(dev):
+        offs = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        offs[1:] = torch.cumsum(n_rel, 0)          # the exclusive scan of the counts, on the device
+        i64 = dict(dtype=torch.int64, device=dev)
+        recv, send, rev_edge = torch.empty((n_total,), **i64), torch.empty((n_total,), **i64), torch.empty((n_total,), **i64)
+        row_start, rev_ptr = torch.empty((B * n_rows + 1,), **i64), torch.empty((B * n_rows + 1,), **i64)
+        _check(lib.gsr_dyn_batch_graph(B, int(n_rows), max_nR, _ptr(recv_pad), _ptr(send_pad), _ptr(n_rel), _ptr(offs), _ptr(recv), _ptr(send),
+                                       _ptr(row_start), _ptr(rev_ptr), _ptr(rev_edge), _stream(dev)), "gsr_dyn_batch_graph")
+    return recv, send, row_start, rev_ptr, rev_edge
 
 
 def plan_step_head(hist, eef_hist, eef_delta, attrs, instance, with_state: bool):

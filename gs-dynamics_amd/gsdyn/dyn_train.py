@@ -8,8 +8,12 @@ b N, padded relations dropped, relations stably sorted by receiver, built ONCE p
 propagation with kernels for the two steps between the matrix products, forward and backward.  Its gradients are sums in a fixed order
 (no atomics) and bit-identical from run to run; the eager path's scatter_add / index backward are not.
 
+A batch of ``gsdyn.make_dynamics_batch`` carries that graph already (key ``graph``, built by a kernel from the relation lists): the device
+path then uses it as it is -- no ``nonzero``, no sort, no host read -- and the dense ``Rr`` / ``Rs`` may be absent (``dense=False``): the
+length term divides by B x ``n_rel_rows``, the eager path builds the matrices from the padded lists ``receivers`` / ``senders``.
+
 ``DEVICE_PATH_DEFAULT`` is what ``device_path=None`` means; DESIGN.md section 3m has the measurement that decided it.
-Out of scope here: rigid_loss / Umeyama, l1_loss, the dataset and its loader, checkpoints, plots."""
+Out of scope here: rigid_loss / Umeyama, l1_loss, reading episode files (the batches themselves: ``gsdyn.dyn_data``), checkpoints, plots."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
@@ -25,7 +29,9 @@ def _device_path_ok(model: DynamicsPredictor, batch: Dict) -> bool:
     state, attrs, inst = batch["state"], batch["attrs"], batch["p_instance"]
     if not (state.is_cuda and state.dtype == torch.float32 and attrs.dtype == torch.float32 and model.split_grad_ok(attrs)):
         return False
-    if attrs.requires_grad or inst.requires_grad or batch["Rr"].dtype != torch.float32:
+    if attrs.requires_grad or inst.requires_grad or ("Rr" in batch and batch["Rr"].dtype != torch.float32):
+        return False
+    if "Rr" not in batch and "graph" not in batch:
         return False
     return all(p.device == state.device and p.dtype == torch.float32 for p in model.parameters())
 
@@ -42,9 +48,18 @@ def _next_history(state, pred, tool_next):
     return torch.cat([state[:, 1:], torch.cat([pred, tool_next[:, n_p:]], 1)[:, None]], 1)
 
 
+def _dense_relations(batch):
+    """The batch's one-hot ``Rr`` / ``Rs`` [B, n_rel_rows, N]: its own, or built from the padded lists (padding = N: an all-zero row)."""
+    if "Rr" in batch:
+        return batch["Rr"], batch["Rs"]
+    N, dt = batch["state"].shape[2], batch["state"].dtype
+    hot = lambda idx: torch.nn.functional.one_hot(idx, N + 1)[..., :N].to(dt)  # noqa: E731
+    return hot(batch["receivers"]), hot(batch["senders"])
+
+
 def _eager_loss(model, batch, n_future, mse_weight, length_weight):
     state, action = batch["state"], batch.get("action")
-    Rr, Rs = batch["Rr"], batch["Rs"]
+    Rr, Rs = _dense_relations(batch)
     B, n_rel, N = Rr.shape
     recv, send, w = model._indices(Rr, Rs)
     bidx = torch.arange(B, device=state.device)[:, None]
@@ -66,14 +81,19 @@ def _eager_loss(model, batch, n_future, mse_weight, length_weight):
 def _device_loss(model, batch, n_future, mse_weight, length_weight):
     c = model.model_config
     state, action, attrs, inst = batch["state"], batch.get("action"), batch["attrs"], batch["p_instance"]
-    Rr, Rs = batch["Rr"], batch["Rs"]
-    B, n_rel, N = Rr.shape
     dev, n_his = state.device, state.shape[1]
     # ---- the batch's graphs as one block-diagonal graph, once (the relations do not change over the n_future steps)
-    recv, send, w = model._indices(Rr, Rs)
-    b, r = torch.nonzero(w > 0, as_tuple=True)                   # the one host read of the batch: the relation count
-    recv, order = torch.sort(recv[b, r] + b * N, stable=True)    # batch-major already; within a receiver the dataset's row order stays
-    graph = split_graph(recv, (send[b, r] + b * N)[order], B * N)
+    if "graph" in batch:                                             # gsdyn.make_dynamics_batch built it: nothing to derive, no host read
+        graph = batch["graph"]
+        B, N = state.shape[0], state.shape[2]
+        n_rel = batch["Rr"].shape[1] if "Rr" in batch else int(batch["n_rel_rows"])
+    else:
+        Rr, Rs = batch["Rr"], batch["Rs"]
+        B, n_rel, N = Rr.shape
+        recv, send, w = model._indices(Rr, Rs)
+        b, r = torch.nonzero(w > 0, as_tuple=True)                   # the one host read of the batch: the relation count
+        recv, order = torch.sort(recv[b, r] + b * N, stable=True)    # batch-major already; within a receiver the dataset's row order stays
+        graph = split_graph(recv, (send[b, r] + b * N)[order], B * N)
     a = attrs.reshape(B * N, attrs.shape[2]).contiguous()
     g = torch.cat([inst, inst.new_zeros((B, N - inst.shape[1], inst.shape[2]))], 1).reshape(B * N, inst.shape[2]).contiguous()
     none = a.new_zeros((B * N, 0))
@@ -101,7 +121,8 @@ def _device_loss(model, batch, n_future, mse_weight, length_weight):
 def dynamics_loss(model: DynamicsPredictor, batch: Dict, *, n_future: int, mse_weight: float = 1.0, length_weight: float = 0.01,
                   device_path: Optional[bool] = None) -> Tuple[torch.Tensor, Dict]:
     """The training loss of one batch of the reference's dataset dictionary: ``state`` [B, n_his, N, 3], ``attrs`` [B, N, attr_dim],
-    ``p_instance`` [B, n_p, G], ``action`` [B, N, 3], dense ``Rr`` / ``Rs`` [B, n_rel, N] (all-zero rows are padding), ``state_future``
+    ``p_instance`` [B, n_p, G], ``action`` [B, N, 3], dense ``Rr`` / ``Rs`` [B, n_rel, N] (all-zero rows are padding; a batch of
+    ``gsdyn.make_dynamics_batch`` may carry ``graph``, ``receivers`` / ``senders`` and ``n_rel_rows`` instead), ``state_future``
     [B, >= n_future, n_p, 3], ``tool_future`` / ``action_future`` [B, >= n_future - 1, N, 3].  ``n_future`` predictions; each becomes the
     newest frame of the next step's history (the tools' rows from ``tool_future``, the action from ``action_future``); every step adds
     mse_weight x mse(prediction, state_future) + length_weight x mse of the relations' lengths against the oldest history frame.  The

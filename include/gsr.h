@@ -715,6 +715,41 @@ int gsr_views_loss_backward(const float* window11_host, const gsr_loss_views* vi
                             const float* fE, const float* grad_total, float w_l1, float w_ssim, float* d_renders, float* partials,
                             float* d_cam_m, float* d_cam_c, void* stream);
 
+/* ---- training batches of the propagation network (csrc/gsr_dyn_batch.hip; gsdyn.make_dynamics_batch; the reference's
+ * DynDataset.__getitem__, /root/reference/src/data/dataset.py:332-516, for B samples at once).  Additive to ABI 125 (no existing symbol
+ * changed).  N = max_nobj + 1 rows per sample, the one tool in the last row.  Every operation is fp32 and unfused; no atomics, no sort:
+ * bit-identical from run to run, and a sample's outputs depend neither on B nor on its position in the batch.
+ * gsr_dyn_batch_sample: particles [F, P, 3], eef [F, 3], pairs [B, n_his + n_future] (frame indices, clamped to [0, F)), n_particles [B]
+ *   (NULL: P; clamped to [0, P]; 0 gives a sample without objects), start_idx / thin_start [B] (clamped into range), fps_radius [B], rot
+ *   [B, 3, 3], noise [B, n_his, N, 3] or NULL.  One workgroup per sample: gsr_fps_thin's sampling and thinning (same arithmetic, same picks)
+ *   of frame pairs[b, n_his - 1] over the first n_particles[b] rows, min(max_nobj, n_particles[b]) picks; the kept particles, in thinning
+ *   order, are rows 0 .. n_obj[b] - 1 of every frame.  state [B, n_his, N, 3] (objects, zero rows, tool; + noise on every row; then x rot
+ *   with out[c] = (x0 r[0][c] + x1 r[1][c]) + x2 r[2][c]), action [B, N, 3] (the tool's step from frame n_his - 1 to n_his, rotated),
+ *   tool_future / action_future [B, n_future - 1, N, 3], state_future [B, n_future, max_nobj, 3], attrs [B, N, 2], p_instance [B, max_nobj],
+ *   obj_mask [B, max_nobj] (bytes), n_obj [B], fps_idx [B, max_nobj] (particle indices, -1 behind n_obj).
+ *   1 <= P <= GSR_DYN_MAX_P, 1 <= max_nobj <= GSR_DYN_MAX_NOBJ, no NULL pointer but the optional ones: -2 and no launch otherwise.
+ * gsr_dyn_batch_relations: state as above; the relations of its last history frame under gsr_construct_edges' rule with PER-SAMPLE n_obj[b]
+ *   and thresh_sq = adj_thresh[b] * adj_thresh[b]; connect_all != 0 relates every real object with the tool in both directions whatever the
+ *   distance (never the tool with itself).  receivers / senders [B, max_nR]: LOCAL rows in the adjacency matrix's row-major order, padded
+ *   with N; n_rel [B] = the TRUE count (entries beyond max_nR are dropped: the caller checks); Rr / Rs [B, max_nR, N] (both or neither,
+ *   zeroed by the caller): the ones of the one-hot matrices of the same lists.  1 <= topk <= 16.
+ * gsr_dyn_batch_graph: the B padded lists as one block-diagonal graph of B n_rows rows (gsdyn.dynamics.SplitGraph): n_rel [B] (each <=
+ *   max_nR), offsets [B + 1] = their exclusive scan ON THE DEVICE -> receivers / senders [E] (global rows b n_rows + local), row_start and
+ *   rev_ptr [B n_rows + 1], rev_edge [E] (per sender the entry ids ascending, found by a column walk of the padded list). */
+#define GSR_DYN_MAX_P 1024
+#define GSR_DYN_MAX_NOBJ 255
+int gsr_dyn_batch_sample(int32_t B, int32_t F, int32_t P, int32_t n_his, int32_t n_future, int32_t max_nobj, const float* particles,
+                         const float* eef, const int64_t* pairs, const int32_t* n_particles, const int32_t* start_idx, const int32_t* thin_start,
+                         const float* fps_radius, const float* rot, const float* noise, float* state, float* action, float* tool_future,
+                         float* action_future, float* state_future, float* attrs, float* p_instance, uint8_t* obj_mask, int32_t* n_obj,
+                         int64_t* fps_idx, void* stream);
+int gsr_dyn_batch_relations(int32_t B, int32_t n_his, int32_t max_nobj, const float* state, const int32_t* n_obj, const float* adj_thresh,
+                            int32_t topk, int32_t connect_all, int32_t max_nR, int64_t* receivers, int64_t* senders, int32_t* n_rel, float* Rr,
+                            float* Rs, void* stream);
+int gsr_dyn_batch_graph(int32_t B, int32_t n_rows, int32_t max_nR, const int64_t* receivers_padded, const int64_t* senders_padded,
+                        const int32_t* n_rel, const int64_t* offsets, int64_t* receivers, int64_t* senders, int64_t* row_start,
+                        int64_t* rev_ptr, int64_t* rev_edge, void* stream);
+
 /* ---- mark_visible  (replaces `mark_visible`; GaussianRasterizer.markVisible).  present[P] = view z > 0.2 */
 int gsr_mark_visible(const float* viewmatrix, int32_t P, const float* means3D, uint8_t* present, void* stream);
 
