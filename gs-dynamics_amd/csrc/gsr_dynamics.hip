@@ -8,6 +8,7 @@
 #include "gsr_common.h"
 #include "gsr_relations.h"
 #include "gsr_fps_thin.h"
+#include "gsr_svd3.h"
 
 // kernels live in a NAMED namespace: profilers and traces show gsr_dynamics::<kernel>, not "(anonymous namespace)"
 namespace gsr_dynamics {
@@ -381,26 +382,7 @@ __device__ __forceinline__ int fit_one_rotation(const float* Fb, float n, float*
     for (int j = 0; j < 3; ++j) { A[i][j] = (double)Fb[3 * i + j]; V[i][j] = i == j ? 1.0 : 0.0; zero = zero && A[i][j] == 0.0; }
   auto identity = [&](int c) { for (int i = 0; i < 9; ++i) Rb[i] = (i % 4 == 0) ? 1.0f : 0.0f; return c; };
   if (n <= 0.0f || zero) return identity(0);
-  for (int sweep = 0; sweep < 40; ++sweep) {            // A V0 = U S: rotate column pairs until they are orthogonal
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int i = 0; i < 3; ++i) { al += A[i][p] * A[i][p]; be += A[i][q] * A[i][q]; ga += A[i][p] * A[i][q]; }
-        if (ga == 0.0 || fabs(ga) <= 1e-17 * sqrt(al * be)) continue;
-        off = fmax(off, fabs(ga) / sqrt(al * be));
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int i = 0; i < 3; ++i) {
-          const double ap = A[i][p], aq = A[i][q];
-          A[i][p] = c * ap - s * aq; A[i][q] = s * ap + c * aq;
-          const double vp = V[i][p], vq = V[i][q];
-          V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
+  gsr_svd3_jacobi(A, V);                               // A V0 = U S: rotate column pairs until they are orthogonal (gsr_svd3.h)
   double sg[3];
   for (int j = 0; j < 3; ++j) sg[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
   int o0 = 0, o1 = 1, o2 = 2;                          // descending order of the singular values

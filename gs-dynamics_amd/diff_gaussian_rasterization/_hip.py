@@ -98,7 +98,7 @@ EXPORTS = ("gsr_version", "gsr_last_error", "gsr_geom_bytes", "gsr_image_bytes",
            "gsr_plan_cost_grad", "gsr_knn_scratch_bytes", "gsr_knn",
            "gsr_voxel_scratch_bytes", "gsr_voxel_points", "gsr_voxel_depth_views",
            "gsr_gnn_aggregate_backward", "gsr_gnn_rel_inputs_backward",
-           "gsr_dyn_batch_sample", "gsr_dyn_batch_relations", "gsr_dyn_batch_graph")
+           "gsr_dyn_batch_sample", "gsr_dyn_batch_relations", "gsr_dyn_batch_graph", "gsr_rigid_fit")
 
 
 def load_library():
@@ -253,6 +253,8 @@ def load_library():
     lib.gsr_dyn_batch_relations.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.gsr_dyn_batch_graph.restype = C.c_int
     lib.gsr_dyn_batch_graph.argtypes = [i32, i32, i32] + [vp] * 10
+    lib.gsr_rigid_fit.restype = C.c_int
+    lib.gsr_rigid_fit.argtypes = [i32, i32] + [vp] * 11
     lib.gsr_fit_bones.restype = C.c_int
     lib.gsr_fit_bones.argtypes = [i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.gsr_lbs.restype = C.c_int
@@ -1265,6 +1267,38 @@ def dyn_batch_graph(recv_pad, send_pad, n_rel, n_rows: int, n_total: int):
         _check(lib.gsr_dyn_batch_graph(B, int(n_rows), max_nR, _ptr(recv_pad), _ptr(send_pad), _ptr(n_rel), _ptr(offs), _ptr(recv), _ptr(send),
                                        _ptr(row_start), _ptr(rev_ptr), _ptr(rev_edge), _stream(dev)), "gsr_dyn_batch_graph")
     return recv, send, row_start, rev_ptr, rev_edge
+
+
+def rigid_fit(X, Y, mask):
+    """gsr_rigid_fit (include/gsr.h): X, Y [B, N, 3] contiguous float32 and mask [B, N] contiguous bool on one HIP device -> dict(R [B, 3, 3],
+    t [B, 1, 3], aligned, residual [B, N, 3], sse [B] fp32; count, code [B] int32).  One launch, no host read.  ``ValueError`` for any other
+    dtype, shape, layout or device.  B = 0 or N = 0: empty / zero outputs (R = I, t = 0, code = 1) without a library call."""
+    for name, v in (("X", X), ("Y", Y), ("mask", mask)):
+        if not isinstance(v, torch.Tensor):
+            raise ValueError(f"rigid_fit: {name} must be a tensor")
+    if X.dim() != 3 or X.shape[2] != 3 or tuple(Y.shape) != tuple(X.shape) or tuple(mask.shape) != tuple(X.shape[:2]):
+        raise ValueError(f"rigid_fit: X, Y [B, N, 3] and mask [B, N], please (got {tuple(X.shape)}, {tuple(Y.shape)}, {tuple(mask.shape)})")
+    if X.dtype != torch.float32 or Y.dtype != torch.float32 or mask.dtype != torch.bool:
+        raise ValueError(f"rigid_fit: float32 X, Y and a bool mask, please (got {X.dtype}, {Y.dtype}, {mask.dtype})")
+    if not (X.is_cuda and Y.device == X.device and mask.device == X.device):
+        raise ValueError(f"rigid_fit: X, Y and mask on one HIP device, please (got {X.device}, {Y.device}, {mask.device})")
+    if not (X.is_contiguous() and Y.is_contiguous() and mask.is_contiguous()):
+        raise ValueError("rigid_fit: contiguous tensors, please")
+    dev = X.device
+    B, N = int(X.shape[0]), int(X.shape[1])
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    with _on(dev):
+        if B == 0 or N == 0:
+            return dict(R=torch.eye(3, **f32).repeat(B, 1, 1), t=torch.zeros((B, 1, 3), **f32), aligned=torch.empty((B, N, 3), **f32),
+                        residual=torch.empty((B, N, 3), **f32), sse=torch.zeros((B,), **f32), count=torch.zeros((B,), **i32),
+                        code=torch.ones((B,), **i32))
+        lib = load_library()
+        out = dict(R=torch.empty((B, 3, 3), **f32), t=torch.empty((B, 1, 3), **f32), aligned=torch.empty((B, N, 3), **f32),
+                   residual=torch.empty((B, N, 3), **f32), sse=torch.empty((B,), **f32), count=torch.empty((B,), **i32),
+                   code=torch.empty((B,), **i32))
+        _check(lib.gsr_rigid_fit(B, N, _ptr(X), _ptr(Y), _ptr(mask), _ptr(out["R"]), _ptr(out["t"]), _ptr(out["aligned"]), _ptr(out["residual"]),
+                                 _ptr(out["sse"]), _ptr(out["count"]), _ptr(out["code"]), _stream(dev)), "gsr_rigid_fit")
+    return out
 
 
 def plan_step_head(hist, eef_hist, eef_delta, attrs, instance, with_state: bool):

@@ -14,4 +14,5 @@ from .knn import knn_points  # noqa: F401
 from .observe import voxel_down_sample, depth_to_cloud, observe_state  # noqa: F401
 from .dyn_train import dynamics_loss, train_dynamics_step  # noqa: F401
 from .dyn_data import make_dynamics_batch, draw_batch_randomness  # noqa: F401
+from .rigid_fit import umeyama_fit  # noqa: F401
 from .train import train, train_timestep, initialize_per_timestep, initialize_post_first_timestep, params2cpu, save_params  # noqa: F401

@@ -750,6 +750,25 @@ int gsr_dyn_batch_graph(int32_t B, int32_t n_rows, int32_t max_nR, const int64_t
                         const int32_t* n_rel, const int64_t* offsets, int64_t* receivers, int64_t* senders, int64_t* row_start,
                         int64_t* rev_ptr, int64_t* rev_edge, void* stream);
 
+/* ---- rigid alignment of the training loss (csrc/gsr_rigid_fit.hip; gsdyn.umeyama_fit; the reference's
+ * umeyama_algorithm(fixed_scale=True), src/gnn/utils.py:7-40, as rigid_loss uses it, src/train.py:32-40).  Additive to ABI 125 (no existing
+ * symbol changed).  One launch, one wave per sample; fp64 sums in a fixed order (a lane's rows ascending, then an xor butterfly), the fp64
+ * Jacobi sweep of csrc/gsr_svd3.h; no atomics, no host read: bit-identical from run to run, and a sample's outputs depend neither on B nor
+ * on its position in the batch.
+ * gsr_rigid_fit: X, Y [B, N, 3], mask [B, N] (one byte per row, non-zero = the row counts) -> per sample the rotation R [B, 3, 3] and
+ *   translation t [B, 3] that take the masked rows of X onto those of Y in the least-squares sense, aligned [B, N, 3] = X R^T + t (every
+ *   row), residual [B, N, 3] = Y - aligned on the masked rows and exactly 0 elsewhere, sse [B] = the sum of residual^2, count [B] = the
+ *   number n of masked rows, code [B].  With mu_x, mu_y the masked means, C = (1 / n) sum (Y - mu_y)(X - mu_x)^T and s1 >= s2 >= s3 its
+ *   singular values (u_i, v_i its vectors):
+ *     n >= 3 and s2 > 3 * 2^-23 * s1 : R = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T, t = mu_y - R mu_x                      code 0
+ *     otherwise (rank <= 1 or n < 3)  : R = I, t = mu_y - mu_x                                                               code 1
+ *     n = 0                           : R = I, t = 0, sse = 0                                                                code 1
+ *     a non-finite masked value       : R, t, aligned, the masked rows of residual and sse are NaN; other samples untouched  code 1
+ *   Everything is computed in fp64 from the fp32 inputs and rounded to fp32 once (residual from the fp64 R, t, not from their rounded
+ *   values).  B, N >= 1, no NULL pointer: -2 and no launch otherwise. */
+int gsr_rigid_fit(int32_t B, int32_t N, const float* X, const float* Y, const uint8_t* mask, float* R, float* t, float* aligned,
+                  float* residual, float* sse, int32_t* count, int32_t* code, void* stream);
+
 /* ---- mark_visible  (replaces `mark_visible`; GaussianRasterizer.markVisible).  present[P] = view z > 0.2 */
 int gsr_mark_visible(const float* viewmatrix, int32_t P, const float* means3D, uint8_t* present, void* stream);
 
